@@ -21,12 +21,60 @@ t_step = max over ranks. algbw is the standard per-collective algorithmic
 bandwidth (nccl-tests convention) — NOT multiplied by N. n_gpus=1
 degenerates to the library's local-copy path (algbw = copy bandwidth) and
 is reported as such in config.note.
+
+A plain run sets up, warms up, times --steps steps and prints the result
+line. --dump-outputs DIR additionally saves the last timed step's receive
+buffer (a fixed seeded sample when it is large) so two builds can be
+compared output for output; the message is seeded, so the inputs repeat
+from run to run. --full is reserved for measurements beyond the
+headline; every such measurement of this project is a script of its own
+under benchmarks/, so --full adds nothing here.
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+# --dump-outputs writes the whole result up to this many elements, and a
+# fixed, seeded sample of that many elements of a larger one (16 MiB fp32).
+DUMP_MAX_ELEMS = 1 << 22
+# Seed of the synthetic message (rank r draws with INPUT_SEED + r).
+INPUT_SEED = 0
+
+
+def dump_sample_indices(count):
+    """Indices of the dumped sample of a `count`-element result, or None
+    when the whole result is dumped. Stratified: the buffer is cut into
+    DUMP_MAX_ELEMS equal strata and one seeded position is taken in each,
+    so the indices are distinct, sorted and spread over the whole buffer;
+    the first and last element are always included."""
+    import numpy as np
+    if count <= DUMP_MAX_ELEMS:
+        return None
+    m = DUMP_MAX_ELEMS
+    edges = np.arange(m + 1, dtype=np.int64) * count // m
+    width = np.diff(edges)
+    frac = np.random.RandomState(12345).random_sample(m)
+    idx = edges[:-1] + np.minimum((frac * width).astype(np.int64), width - 1)
+    idx[0], idx[-1] = 0, count - 1
+    return idx
+
+
+def dump_outputs(dirname, out, count):
+    """Write the receive buffer of the last timed step (what a caller of
+    the allreduce gets back) as DIR/allreduce_out.npy, float32."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    idx = dump_sample_indices(count)
+    if isinstance(out, np.ndarray):
+        arr = out if idx is None else out[idx]
+    else:
+        import torch
+        sel = out if idx is None else out[torch.from_numpy(idx).to(out.device)]
+        arr = sel.cpu().numpy()
+    np.save(os.path.join(dirname, "allreduce_out.npy"),
+            np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def main():
@@ -37,7 +85,16 @@ def main():
     ap.add_argument("--mbytes", type=int, default=256, help="message MiB (fp32)")
     ap.add_argument("--device", default="auto", choices=["auto", "cuda", "cpu"])
     ap.add_argument("--algo", default=None, help="MLSL_ALLREDUCE_ALGO override")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step produced as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (this benchmark has none: the sweeps, "
+                         "roofline and comparison runs live in benchmarks/)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.algo:
         os.environ["MLSL_ALLREDUCE_ALGO"] = args.algo
@@ -70,11 +127,15 @@ def main():
     if use_cuda:
         local = int(os.environ.get("LOCAL_RANK", rank))
         torch.cuda.set_device(local % torch.cuda.device_count())
-        buf = torch.randn(count, dtype=torch.float32, device="cuda")
+        # seeded per rank: the same arguments give the same message every run
+        gen = torch.Generator(device="cuda")
+        gen.manual_seed(INPUT_SEED + rank)
+        buf = torch.randn(count, dtype=torch.float32, device="cuda",
+                          generator=gen)
         out = torch.empty_like(buf)
     else:
         import numpy as np
-        buf = np.random.randn(count).astype(np.float32)
+        buf = np.random.RandomState(INPUT_SEED + rank).randn(count).astype(np.float32)
         out = np.empty_like(buf)
 
     d = mx.Distribution(size, 1)
@@ -120,6 +181,9 @@ def main():
     # Pinned metric (see module docstring): algbw = S/t, busbw = 2(n-1)/n * algbw.
     algbw = msg_bytes / (elapsed_max / args.steps) / 1e9
     busbw = (2.0 * (size - 1) / size) * algbw if size > 1 else 0.0
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, count)
 
     if rank == 0:
         out = {
