@@ -40,7 +40,7 @@ def main():
     torch.cuda.synchronize()
 
     for _ in range(ITERS):
-        ops.reduce_(a, b, n)          # ReduceF32NTKernel (>=16 MiB -> NT)
+        ops.reduce_(a, b, n)          # ReduceF32Kernel<SUM, NT> (>=16 MiB -> NT)
     for _ in range(ITERS):
         ops.copy(a, b, n * 4)         # CopyNTKernel
     for _ in range(ITERS):
@@ -53,7 +53,7 @@ def main():
     wireb = torch.empty(ops.wire_bytes(n), device="cuda", dtype=torch.uint8)
     outb = torch.empty_like(abf)
     for _ in range(ITERS):
-        ops.quantize(abf, wireb, n, err=errb, dtype="bf16")  # QuantizeBf16x2Kernel
+        ops.quantize(abf, wireb, n, err=errb, dtype="bf16")  # QuantizeX2Kernel<bf16>
     for _ in range(ITERS):
         ops.dequantize(wireb, outb, n, dtype="bf16")  # DequantizeBf16x2Kernel
     # pack: half the fms of a 256 MiB block (PackFastKernel<uint4,NT>)

@@ -415,15 +415,20 @@ void P2pGroup::IssueSchedule(CommRequest* req, ChunkExec& ce, size_t lane,
                         continue;
                     }
                     if (!quant || (!rj.fuse_into && !rj.fuse_out)) {
-                        // mode 0 (byte copy) is dtype-agnostic, so quant AG
+                        // COPY (byte copy) is dtype-agnostic, so quant AG
                         // forwards ride it too
-                        const int mode = rj.fuse_into ? 1 : (rj.fuse_out ? 2 : 0);
-                        uint8_t* d = mode == 1 ? ptr(st.local_dst) + off
-                                               : ptr(st.recv) + off;
-                        const uint8_t* o =
-                            mode == 2 ? ptr(st.local_src) + off : nullptr;
+                        const FusedConsume mode =
+                            rj.fuse_into  ? FusedConsume::REDUCE
+                            : rj.fuse_out ? FusedConsume::REDUCE_OUT
+                                          : FusedConsume::COPY;
+                        uint8_t* d = mode == FusedConsume::REDUCE
+                                         ? ptr(st.local_dst) + off
+                                         : ptr(st.recv) + off;
+                        const uint8_t* o = mode == FusedConsume::REDUCE_OUT
+                                               ? ptr(st.local_src) + off
+                                               : nullptr;
                         if (LaunchXferRecvFused(d, sl, o,
-                                                mode == 0 ? n : n / es,
+                                                mode == FusedConsume::COPY ? n : n / es,
                                                 req->Dtype(), ce.sch.rop, mode,
                                                 &wp, rctr,
                                                 fused_rcvd_[e] += kXferFusedGrid,

@@ -13,12 +13,12 @@ namespace mlsl {
 void LaunchReduce(void* dst, const void* src, size_t count, DataType dt,
                   ReduceOp op, hipStream_t stream);
 
-// dst = a + b elementwise into a third buffer (out-of-place variant used by
-// fused pipelines).
 // f32 SUM with nontemporal loads/stores (A/B benchmarking).
 void LaunchReduceNT(void* dst, const void* src, size_t count, hipStream_t stream);
 void LaunchReduceNT2(void* dst, const void* src, size_t count, hipStream_t stream);
 
+// dst = a + b elementwise into a third buffer (out-of-place variant used by
+// fused pipelines).
 void LaunchReduceOut(void* dst, const void* a, const void* b, size_t count,
                      DataType dt, ReduceOp op, hipStream_t stream);
 
@@ -79,7 +79,8 @@ struct XferPoll {
     void* status;
     uint64_t max_ticks;
 };
-// Streaming byte copy with optional poll prologue (NT, 16-B lanes).
+// Streaming byte copy with optional poll prologue (16-B lanes; NT loads of
+// the local source, plain stores into the hand-off slot).
 void LaunchXferCopy(void* dst, const void* src, size_t bytes,
                     const XferPoll* poll, hipStream_t stream);
 // dst op= slot (other==null) or dst = slot op other, with optional poll.
@@ -93,10 +94,11 @@ bool LaunchXferReduce(void* dst, const void* slot, const void* other, size_t n,
 // completion counter + flag publish, in ONE launch with a bounded grid
 // (spinners can never starve the peer's kernels). ctr_target is the
 // ABSOLUTE cumulative workgroup-add count for that counter (the host
-// accumulates kXferFusedGrid / kFanWgsPerPeer per emitted kernel, so
+// accumulates kXferFusedGrid / FanOutWgsPerPeer() per emitted kernel, so
 // kernels with different grids can share an edge counter).
-// Recv `mode`: 0 copy (n = BYTES), 1 reduce-into, 2 reduce-out (n =
-// elements); returns false for uncovered dtypes.
+// Recv `mode`: COPY (n = BYTES), REDUCE into dst, REDUCE_OUT = slot op
+// other (n = elements); returns false for uncovered dtypes.
+enum class FusedConsume : int { COPY = 0, REDUCE = 1, REDUCE_OUT = 2 };
 constexpr uint32_t kXferFusedGrid = 32;   // wgs per fused send/recv kernel
 // wgs per peer in the fan-out: full grid for one peer, split for many
 int FanOutWgsPerPeer(int npeers);
@@ -104,7 +106,7 @@ void LaunchXferSendFused(void* slot, const void* src, size_t bytes,
                          const XferPoll* bp, void* ctr, uint64_t ctr_target,
                          void* in_mbox, uint64_t seq, hipStream_t stream);
 bool LaunchXferRecvFused(void* dst, const void* slot, const void* other,
-                         size_t n, DataType dt, ReduceOp op, int mode,
+                         size_t n, DataType dt, ReduceOp op, FusedConsume mode,
                          const XferPoll* wp, void* ctr, uint64_t ctr_target,
                          void* ack_mbox, uint64_t seq, hipStream_t stream);
 

@@ -23,7 +23,7 @@ void LaunchWaitFlag(const void*, uint64_t, const void*, void*, uint64_t, hipStre
 void LaunchSetFlag(void*, uint64_t, hipStream_t) STUB()
 void LaunchXferCopy(void*, const void*, size_t, const XferPoll*, hipStream_t) STUB()
 void LaunchXferSendFused(void*, const void*, size_t, const XferPoll*, void*, uint64_t, void*, uint64_t, hipStream_t) STUB()
-bool LaunchXferRecvFused(void*, const void*, const void*, size_t, DataType, ReduceOp, int, const XferPoll*, void*, uint64_t, void*, uint64_t, hipStream_t) STUB()
+bool LaunchXferRecvFused(void*, const void*, const void*, size_t, DataType, ReduceOp, FusedConsume, const XferPoll*, void*, uint64_t, void*, uint64_t, hipStream_t) STUB()
 int FanOutWgsPerPeer(int npeers) { return npeers <= 1 ? 32 : npeers <= 4 ? 8 : 4; }
 void LaunchXferRecvQuantAccum(void*, const void*, size_t, size_t, const XferPoll*, void*, uint64_t, void*, uint64_t, hipStream_t) STUB()
 void LaunchFanOutSend(const void*, size_t, const FanPeer*, int, const XferPoll*, hipStream_t) STUB()

@@ -29,15 +29,42 @@ class TestKernels:
         torch.cuda.synchronize()
         assert torch.allclose(a, want)
 
-    @pytest.mark.parametrize("n", [4096, (1 << 20) + 17])
-    def test_reduce_bf16(self, n):
+    # 4099: vector body plus scalar tail
+    # sum cases keep the ids they had before `op` was a parameter
+    @pytest.mark.parametrize("n,op", [
+        pytest.param(n, op, id=str(n) if op == "sum" else f"{op}-{n}")
+        for op in ("sum", "min", "max") for n in (4096, 4099, (1 << 20) + 17)])
+    def test_reduce_bf16(self, n, op):
         from mlsl_amd import ops
         a = torch.randn(n, device="cuda", dtype=torch.bfloat16)
         b = torch.randn(n, device="cuda", dtype=torch.bfloat16)
-        want = (a.float() + b.float()).to(torch.bfloat16)
-        ops.reduce_(a, b, n, dtype="bf16", op="sum")
+        af, bf = a.float(), b.float()
+        want = {"sum": af + bf, "min": torch.minimum(af, bf),
+                "max": torch.maximum(af, bf)}[op].to(torch.bfloat16)
+        ops.reduce_(a, b, n, dtype="bf16", op=op)
         torch.cuda.synchronize()
         assert torch.allclose(a.float(), want.float(), atol=0.0, rtol=0.0)
+
+    def test_reduce_f16(self):
+        from mlsl_amd import ops
+        n = 1027
+        a = torch.randn(n, device="cuda", dtype=torch.float16)
+        b = torch.randn(n, device="cuda", dtype=torch.float16)
+        want = (a.float() + b.float()).half()
+        ops.reduce_(a, b, n, dtype="f16", op="sum")
+        torch.cuda.synchronize()
+        assert torch.equal(a, want)
+
+    @pytest.mark.parametrize("dtype,name", [(torch.uint8, "u8"), (torch.int64, "i64")])
+    def test_reduce_integers(self, dtype, name):
+        from mlsl_amd import ops
+        n = 1027
+        a = torch.randint(0, 100, (n,), device="cuda", dtype=dtype)
+        b = torch.randint(0, 100, (n,), device="cuda", dtype=dtype)
+        want = a + b  # < 200: no u8 overflow
+        ops.reduce_(a, b, n, dtype=name, op="sum")
+        torch.cuda.synchronize()
+        assert torch.equal(a, want)
 
     @pytest.mark.parametrize("n", [4096])
     def test_reduce_f64_i32(self, n):
@@ -54,14 +81,13 @@ class TestKernels:
         assert torch.allclose(a, want)
         assert torch.equal(a32, want32)
 
-    @pytest.mark.parametrize("n,block", [(1 << 20, 256), (100_000, 256), (5000, 512),
-                                         (1 << 21, 256)])  # >=4MiB: f32 x2 fast path
-    def test_quant_roundtrip_f32(self, n, block):
+    @staticmethod
+    def _roundtrip_f32(n, block, use_err=True, out=None):
         from mlsl_amd import ops
         g = torch.randn(n, device="cuda") * 3.0
         wire = torch.empty(ops.wire_bytes(n, block), device="cuda", dtype=torch.uint8)
-        out = torch.empty_like(g)
-        err = torch.zeros_like(g)
+        out = torch.empty_like(g) if out is None else out
+        err = torch.zeros_like(g) if use_err else None
         ops.quantize(g, wire, n, err=err, block=block)
         ops.dequantize(wire, out, n, block=block)
         torch.cuda.synchronize()
@@ -71,16 +97,40 @@ class TestKernels:
         bound = (scale.expand_as(gb).reshape(-1)[:n] * 0.5) + 1e-7
         assert ((out - g).abs() <= bound + 1e-6).all()
         # error feedback: residual = input - quantized
-        assert torch.allclose(g, out + err, atol=1e-5)
+        if use_err:
+            assert torch.allclose(g, out + err, atol=1e-5)
+        return wire
 
-    @pytest.mark.parametrize("block,n", [(256, 1 << 18), (256, (1 << 18) - 128),
-                                         (128, 1 << 16)])
-    def test_quant_roundtrip_bf16(self, block, n):
-        # (256, 256-multiple) exercises the two-blocks-per-wave bf16 fast
-        # path; the others the generic kernel.
+    @pytest.mark.parametrize("n,block", [(1 << 20, 256), (100_000, 256), (5000, 512),
+                                         (1 << 21, 256),  # >=4MiB: f32 x2 fast path
+                                         ((1 << 20) + 256, 256),  # x2, odd block count
+                                         ((1 << 22) + 100, 256)])  # generic NT dequantize
+    def test_quant_roundtrip_f32(self, n, block):
+        self._roundtrip_f32(n, block)
+
+    @pytest.mark.parametrize("n", [1 << 20, (1 << 20) + 256])
+    def test_quant_x2_no_error_feedback_f32(self, n):
+        # two-blocks-per-wave kernels without the residual; the odd block
+        # count leaves one half-wave of the last pair idle
+        self._roundtrip_f32(n, 256, use_err=False)
+
+    def test_dequantize_unaligned_output(self):
+        # a 4-byte-offset view takes the non-vector store path and must
+        # produce the same values as the aligned one
+        from mlsl_amd import ops
+        n, block = 5000, 256
+        out_full = torch.empty(n + 1, device="cuda")
+        wire = self._roundtrip_f32(n, block, out=out_full[1:])
+        aligned = torch.empty(n, device="cuda")
+        ops.dequantize(wire, aligned, n, block=block)
+        torch.cuda.synchronize()
+        assert torch.equal(out_full[1:], aligned)
+
+    @staticmethod
+    def _roundtrip_bf16(block, n, use_err=True):
         from mlsl_amd import ops
         a = torch.randn(n, device="cuda", dtype=torch.bfloat16)
-        err = torch.zeros(n, device="cuda", dtype=torch.bfloat16)
+        err = torch.zeros(n, device="cuda", dtype=torch.bfloat16) if use_err else None
         wire = torch.empty(ops.wire_bytes(n, block), device="cuda",
                            dtype=torch.uint8)
         ops.quantize(a, wire, n, err=err, block=block, dtype="bf16")
@@ -99,8 +149,21 @@ class TestKernels:
         assert (diff <= err_bound + 1e-6).float().mean().item() > 0.999, \
             f"bf16 roundtrip error too large: {diff.max()}"
         # error feedback: residual + dequant ~= original
-        rec = out.float() + err.float()
-        assert (rec - af).abs().max().item() < 0.05 * af.abs().max().item() + 0.05
+        if use_err:
+            rec = out.float() + err.float()
+            assert (rec - af).abs().max().item() < 0.05 * af.abs().max().item() + 0.05
+
+    @pytest.mark.parametrize("block,n", [(256, 1 << 18), (256, (1 << 18) - 128),
+                                         (128, 1 << 16),
+                                         (256, (1 << 18) + 256)])  # x2, odd block count
+    def test_quant_roundtrip_bf16(self, block, n):
+        # (256, 256-multiple) exercises the two-blocks-per-wave bf16 fast
+        # path; the others the generic kernel.
+        self._roundtrip_bf16(block, n)
+
+    @pytest.mark.parametrize("n", [1 << 18, (1 << 18) + 256])
+    def test_quant_x2_no_error_feedback_bf16(self, n):
+        self._roundtrip_bf16(256, n, use_err=False)
 
     def test_quant_error_feedback_accumulates(self):
         from mlsl_amd import ops
@@ -144,18 +207,37 @@ class TestKernels:
         assert (out - want).abs().max().item() < 4 * step
 
     def test_pack_unpack(self):
+        self._pack_unpack("f32", 12, 0)
+
+    # the case above under its old name, the other layouts here: row bytes
+    # 48 (and offset 32) take the 16-byte-vector kernels; the others the
+    # 4-, 2-, 8- and 1-byte element kernels
+    @pytest.mark.parametrize("dtype,fm_size,buf_offset", [
+        (dt, s, off) for dt, s in (("f32", 12), ("f32", 3), ("bf16", 5), ("f64", 3),
+                                   ("u8", 7))
+        for off in (0, 8) if (dt, s, off) != ("f32", 12, 0)])
+    def test_pack_unpack_layouts(self, dtype, fm_size, buf_offset):
+        self._pack_unpack(dtype, fm_size, buf_offset)
+
+    @staticmethod
+    def _pack_unpack(dtype, fm_size, buf_offset):
         from mlsl_amd import ops
-        mb, fm, s = 8, 16, 12
-        src = torch.randn(mb * fm * s, device="cuda")
-        dst = torch.zeros(4 * 8 * s, device="cuda")
+        tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f64": torch.float64,
+               "u8": torch.uint8}[dtype]
+        mb, fm, s = 8, 16, fm_size
+        src = torch.randint(0, 200, (mb * fm * s,), device="cuda").to(tdt) \
+            if dtype == "u8" else torch.randn(mb * fm * s, device="cuda").to(tdt)
+        dst = torch.zeros(buf_offset + 4 * 8 * s, device="cuda", dtype=tdt)
         kw = dict(mb_offset=2, mb_count=4, fm_offset=4, fm_count=8, fm_size=s,
-                  buf_offset=0, local_fm_count=fm, local_mb_count=mb, dtype="f32")
+                  buf_offset=buf_offset, local_fm_count=fm, local_mb_count=mb,
+                  dtype=dtype)
         ops.pack(src, dst, **kw)
         back = torch.zeros_like(src)
         ops.unpack(dst, back, **kw)
         torch.cuda.synchronize()
         v = src.view(mb, fm, s)[2:6, 4:12, :].reshape(-1)
-        assert torch.equal(dst, v)
+        assert torch.equal(dst[buf_offset:], v)
+        assert not dst[:buf_offset].any()
         assert torch.equal(back.view(mb, fm, s)[2:6, 4:12, :].reshape(-1), v)
 
     def test_reduce_bandwidth_sane(self):

@@ -71,6 +71,15 @@ def test_collectives_multirank(world):
 
 
 @requires_gpu
+def test_collectives_unfused_transport():
+    # fused kernels off: every collective goes through the wait-flag kernel,
+    # the wide copy/reduce kernels (in-place and out-of-place, f32 and bf16)
+    # and the set-flag kernel, which otherwise only large messages reach
+    run_gpu_ranks("gpu_collectives", 2,
+                  extra_env={"MLSL_P2P_FUSED_MAX_KB": "0"})
+
+
+@requires_gpu
 @pytest.mark.parametrize("algo", ["ring", "rhd"])
 def test_allreduce_algos_multislot(algo):
     # 1 MiB slots force 8 sub-messages per 8 MiB segment: slot wrap +

@@ -152,6 +152,32 @@ def gpu_collectives():
         + size * (size - 1) / 2.0
     assert torch.allclose(ob.float(), wb.float()), "bf16 allreduce"
 
+    # min/max and bf16 reduce-out through the transport reduce kernels;
+    # small integers, so every result is exact in its dtype
+    count = 257
+    a = _arange(torch, count, rank)
+    out = torch.empty_like(a)
+    mx.wait(d.all_reduce(a, out, count, op="min", group=g))
+    torch.cuda.synchronize()
+    assert torch.equal(out, _arange(torch, count, 0)), "f32 min allreduce"
+    count = 2048
+    base = torch.arange(count, dtype=torch.bfloat16, device="cuda") % 8
+    for op, extreme in (("min", 0), ("max", size - 1)):
+        ab = base + rank
+        ob = torch.empty_like(ab)
+        mx.wait(d.all_reduce(ab, ob, count, op=op, group=g))
+        torch.cuda.synchronize()
+        assert torch.equal(ob, base + extreme), ("bf16 allreduce", op)
+    per = 1536
+    seg = torch.arange(per, dtype=torch.bfloat16, device="cuda") % 8
+    src = torch.cat([seg + rank + i for i in range(size)])
+    out = torch.empty(per, dtype=torch.bfloat16, device="cuda")
+    mx.wait(d.reduce_scatter(src, out, per, op="sum", group=g))
+    torch.cuda.synchronize()
+    # max value 8*7 + 28 + 8*7 = 140 <= 256: exact in bf16
+    want = size * seg.float() + size * (size - 1) / 2.0 + size * rank
+    assert torch.equal(out.float(), want), "bf16 reduce_scatter"
+
     # p2p ring over send_recv_list
     n = 1024
     dst_rank = (rank + 1) % size
