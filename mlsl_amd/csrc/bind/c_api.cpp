@@ -99,7 +99,8 @@ int mlsl_test(mlsl_request req, int* done, void** result) {
 }
 
 int mlsl_set_quant_params(size_t block_elems) {
-    C_TRY QuantParams p;
+    C_TRY CheckQuantBlock(block_elems, "mlsl_set_quant_params");
+    QuantParams p;
     p.block_elems = block_elems;
     Environment::GetEnv().SetQuantizationParams(p);
     C_CATCH
@@ -829,6 +830,9 @@ int mlsl_environment_set_quantization_params(mlsl_environment, mlsl_quant_params
         if (params->reduce_sum_func_name)
             qp.reduce_fn = params->reduce_sum_func_name;
         if (params->block_size) qp.block_bytes = params->block_size;
+    } else {
+        // built-in codec; a plugin defines its own wire block
+        CheckQuantBlock(qp.block_elems, "mlsl_environment_set_quantization_params");
     }
     Environment::GetEnv().SetQuantizationParams(qp);
     C_CATCH

@@ -6,6 +6,7 @@
 
 #include "../comm/context.hpp"
 #include "../comm/device_comm.hpp"
+#include "../comm/quant.hpp"
 #include "../core/types.hpp"
 #include "../hip/kernels.hpp"
 #include "../include/mlsl/c_api.h"
@@ -110,6 +111,27 @@ int mlsl_hip_dequantize_nt(const void* wire, void* out, size_t count, size_t blo
 int mlsl_hip_quant_accum(void* acc, const void* wire, size_t count, size_t block) {
     OPS_TRY LaunchQuantAccum(acc, wire, count, block, nullptr);
     SyncNullStream();
+    OPS_CATCH
+}
+
+// Host codec (comm/quant.cpp) on host pointers: same wire format and the
+// same argument order as the device ops above.
+int mlsl_host_quantize(const void* in, void* err, void* wire, size_t count,
+                       size_t block, int dt, int use_err) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_quantize");
+    HostQuantize(in, err, wire, count, block, static_cast<DataType>(dt), use_err != 0);
+    OPS_CATCH
+}
+
+int mlsl_host_dequantize(const void* wire, void* out, size_t count, size_t block, int dt) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_dequantize");
+    HostDequantize(wire, out, count, block, static_cast<DataType>(dt));
+    OPS_CATCH
+}
+
+int mlsl_host_quant_accum(void* acc, const void* wire, size_t count, size_t block) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_quant_accum");
+    HostQuantAccum(acc, wire, count, block);
     OPS_CATCH
 }
 

@@ -27,6 +27,7 @@ void Context::Init(int rank, int size) {
     MLSL_CHECK(!initialized_, "Context::Init called twice");
     Config& cfg = GlobalConfig();
     cfg = Config::FromEnv();  // re-read: tests mutate env between inits
+    CheckQuantBlock(cfg.quant_block, "MLSL_QUANT_BLOCK");
     SetLogLevel(static_cast<LogLevel>(cfg.log_level));
 
     InstallSignalHandlers();

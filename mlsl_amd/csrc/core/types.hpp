@@ -128,4 +128,14 @@ class Error : public std::runtime_error {
                                 " — " + (msg));                             \
     } while (0)
 
+// An int8 wire block is [f32 scale][f32 reserved][int8 x block_elems], one
+// after the other: only a non-zero multiple of 4 keeps every block's header
+// (and the 4-byte payload words of the kernels) naturally aligned.
+inline void CheckQuantBlock(size_t block_elems, const char* where) {
+    if (block_elems == 0 || block_elems % 4 != 0)
+        throw Error(std::string(where) + ": quantization block of " +
+                    std::to_string(block_elems) +
+                    " elements is not supported (must be a non-zero multiple of 4)");
+}
+
 }  // namespace mlsl

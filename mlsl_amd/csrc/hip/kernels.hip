@@ -732,6 +732,7 @@ void DequantizeGeneric(const void* wire, void* out, size_t count, size_t block_e
 void LaunchQuantize(const void* in, void* err, void* wire, size_t count,
                     size_t block_elems, DataType dt, bool use_err,
                     hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchQuantize");
     if (dt == DataType::F32)
         QuantizeTyped<float>(in, err, wire, count, block_elems, dt, use_err, stream);
     else if (dt == DataType::BF16)
@@ -743,6 +744,7 @@ void LaunchQuantize(const void* in, void* err, void* wire, size_t count,
 
 void LaunchDequantize(const void* wire, void* out, size_t count,
                       size_t block_elems, DataType dt, hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchDequantize");
     const bool x2 = X2Eligible(count, block_elems, dt, out, nullptr, wire);
     const size_t nblocks = NumBlocks(count, block_elems);
     const uint8_t* w = static_cast<const uint8_t*>(wire);
@@ -783,6 +785,7 @@ void LaunchQuantizeF32NT(const void* in, void* err, void* wire, size_t count,
 
 void LaunchDequantizeNT(const void* wire, void* out, size_t count,
                         size_t block_elems, DataType dt, hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchDequantizeNT");
     // f32-only NT variant (A/B benchmark hook): stream-once wire reads and
     // output stores skip L2 retention.
     if (dt != DataType::F32) {
@@ -795,6 +798,7 @@ void LaunchDequantizeNT(const void* wire, void* out, size_t count,
 
 void LaunchQuantAccum(void* acc_wire, const void* wire, size_t count,
                       size_t block_elems, hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchQuantAccum");
     if (count == 0) return;
     const size_t nblocks = NumBlocks(count, block_elems);
     uint8_t* a = static_cast<uint8_t*>(acc_wire);

@@ -4,7 +4,8 @@ feedback, and pack/unpack. Used by GPU numerics tests and by consumers that
 want the fused kernels without the full Session machinery.
 
 Buffers: torch CUDA tensors, raw integer device pointers, or anything with
-``data_ptr()``.
+``data_ptr()``. The ``host_*`` functions run the host codec of
+csrc/comm/quant.cpp (same wire format) on numpy arrays.
 """
 import ctypes
 
@@ -34,6 +35,11 @@ def _lib():
         L.mlsl_hip_quantize_f32_nt.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p,
                                                c.c_size_t, c.c_size_t]
         L.mlsl_hip_quant_accum.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_size_t]
+        L.mlsl_host_quantize.argtypes = L.mlsl_hip_quantize.argtypes
+        L.mlsl_host_dequantize.argtypes = L.mlsl_hip_dequantize.argtypes
+        L.mlsl_host_quant_accum.argtypes = L.mlsl_hip_quant_accum.argtypes
+        for n in ("mlsl_host_quantize", "mlsl_host_dequantize", "mlsl_host_quant_accum"):
+            getattr(L, n).restype = c.c_int
         ptypes = [c.c_void_p, c.c_void_p] + [c.c_size_t] * 8 + [c.c_int]
         L.mlsl_hip_pack.argtypes = ptypes
         L.mlsl_hip_unpack.argtypes = ptypes
@@ -130,6 +136,51 @@ def quant_accum(acc_wire, wire, count, block=256):
     ap, _ = _as_ptr_dtype(acc_wire)
     wp, _ = _as_ptr_dtype(wire)
     check(_lib().mlsl_hip_quant_accum(ap, wp, count, block))
+
+
+_ELEM_BYTES = {"f32": 4, "bf16": 2}
+
+
+def _host_buf(arr, need_bytes, what):
+    """Pointer of a C-contiguous numpy array holding at least need_bytes."""
+    if not hasattr(arr, "__array_interface__"):
+        raise TypeError(f"{what}: numpy array expected, got {type(arr)}")
+    if not arr.flags["C_CONTIGUOUS"] or arr.nbytes < need_bytes:
+        raise ValueError(f"{what}: need a contiguous array of >= {need_bytes} bytes")
+    return ctypes.c_void_p(arr.__array_interface__["data"][0])
+
+
+def _check_block(block):
+    # the C entry points reject it too; here before wire_bytes() divides by it
+    if block == 0 or block % 4:
+        raise ValueError(f"quantization block of {block} elements is not supported "
+                         "(must be a non-zero multiple of 4)")
+
+
+def host_quantize(inp, wire, count, err=None, block=256, dtype="f32"):
+    """Host codec (csrc/comm/quant.cpp) on numpy arrays; bf16 travels as
+    uint16 bit patterns. Same wire format as `quantize`."""
+    _check_block(block)
+    eb = _ELEM_BYTES[dtype]
+    ip = _host_buf(inp, count * eb, "inp")
+    wp = _host_buf(wire, wire_bytes(count, block), "wire")
+    ep = None if err is None else _host_buf(err, count * eb, "err")
+    check(_lib().mlsl_host_quantize(ip, ep, wp, count, block, DTYPE[dtype],
+                                    1 if err is not None else 0))
+
+
+def host_dequantize(wire, out, count, block=256, dtype="f32"):
+    _check_block(block)
+    wp = _host_buf(wire, wire_bytes(count, block), "wire")
+    op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
+    check(_lib().mlsl_host_dequantize(wp, op_, count, block, DTYPE[dtype]))
+
+
+def host_quant_accum(acc_wire, wire, count, block=256):
+    _check_block(block)
+    ap = _host_buf(acc_wire, wire_bytes(count, block), "acc_wire")
+    wp = _host_buf(wire, wire_bytes(count, block), "wire")
+    check(_lib().mlsl_host_quant_accum(ap, wp, count, block))
 
 
 def pack(src, dst, *, mb_offset, mb_count, fm_offset, fm_count, fm_size,

@@ -219,26 +219,48 @@ class TestKernels:
     def test_pack_unpack_layouts(self, dtype, fm_size, buf_offset):
         self._pack_unpack(dtype, fm_size, buf_offset)
 
+    # the divisions by 1 (FastDiv identity) for fm_size, fm_count and a
+    # single minibatch row; odd sizes in an odd layer through the 4- and
+    # 2-byte element kernels; 64 x 64 x 1024 f32 = 16 MiB inside a 96 x 80
+    # layer through the nontemporal 16-byte arm
+    @pytest.mark.parametrize("dtype,fm_size,shape", [
+        pytest.param("f32", 1, {}, id="fm_size1"),
+        pytest.param("f32", 12, dict(fm_cnt=1), id="fm_count1"),
+        pytest.param("f32", 12, dict(mb_cnt=1), id="mb_count1"),
+        pytest.param("f32", 131, dict(fm=11, fm_cnt=7, fm_off=3), id="odd-f32"),
+        pytest.param("bf16", 131, dict(fm=11, fm_cnt=7, fm_off=3), id="odd-bf16"),
+        pytest.param("f32", 1024, dict(mb=96, fm=80, mb_cnt=64, fm_cnt=64), id="16MiB-nt"),
+    ])
+    def test_pack_unpack_shapes(self, dtype, fm_size, shape):
+        self._pack_unpack(dtype, fm_size, 0, **shape)
+
     @staticmethod
-    def _pack_unpack(dtype, fm_size, buf_offset):
+    def _pack_unpack(dtype, fm_size, buf_offset, mb=8, fm=16, mb_off=2, mb_cnt=4,
+                     fm_off=4, fm_cnt=8):
         from mlsl_amd import ops
         tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "f64": torch.float64,
                "u8": torch.uint8}[dtype]
-        mb, fm, s = 8, 16, fm_size
+        s = fm_size
+        assert mb_off + mb_cnt <= mb and fm_off + fm_cnt <= fm
         src = torch.randint(0, 200, (mb * fm * s,), device="cuda").to(tdt) \
             if dtype == "u8" else torch.randn(mb * fm * s, device="cuda").to(tdt)
-        dst = torch.zeros(buf_offset + 4 * 8 * s, device="cuda", dtype=tdt)
-        kw = dict(mb_offset=2, mb_count=4, fm_offset=4, fm_count=8, fm_size=s,
-                  buf_offset=buf_offset, local_fm_count=fm, local_mb_count=mb,
+        dst = torch.zeros(buf_offset + mb_cnt * fm_cnt * s, device="cuda", dtype=tdt)
+        kw = dict(mb_offset=mb_off, mb_count=mb_cnt, fm_offset=fm_off, fm_count=fm_cnt,
+                  fm_size=s, buf_offset=buf_offset, local_fm_count=fm, local_mb_count=mb,
                   dtype=dtype)
         ops.pack(src, dst, **kw)
         back = torch.zeros_like(src)
         ops.unpack(dst, back, **kw)
         torch.cuda.synchronize()
-        v = src.view(mb, fm, s)[2:6, 4:12, :].reshape(-1)
+        sub = (slice(mb_off, mb_off + mb_cnt), slice(fm_off, fm_off + fm_cnt))
+        v = src.view(mb, fm, s)[sub].reshape(-1)
         assert torch.equal(dst[buf_offset:], v)
         assert not dst[:buf_offset].any()
-        assert torch.equal(back.view(mb, fm, s)[2:6, 4:12, :].reshape(-1), v)
+        assert torch.equal(back.view(mb, fm, s)[sub].reshape(-1), v)
+        # unpack wrote the sub-block and nothing else
+        outside = torch.ones(mb, fm, s, dtype=torch.bool, device="cuda")
+        outside[sub] = False
+        assert not back.view(mb, fm, s)[outside].any()
 
     def test_reduce_bandwidth_sane(self):
         """The f32 reduce kernel should stream well above 1 TB/s on HBM3E
