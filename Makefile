@@ -121,7 +121,8 @@ $(ASAN): mlsl_amd/csrc/tests/schedule_selftest.cpp mlsl_amd/csrc/comm/schedule.c
 # Full-stack ASan: the API selftest (planner+engine+mesh, TCP world
 # matrix) host-compiled with g++ + ASan/UBSan; device kernels stubbed.
 ASAN_API := $(BUILD)/api_selftest_asan
-ASAN_SRC := $(CSRC) mlsl_amd/csrc/tests/api_selftest.cpp             mlsl_amd/csrc/tests/asan_kernel_stubs.cpp
+ASAN_SRC := $(CSRC) mlsl_amd/csrc/tests/api_selftest.cpp             mlsl_amd/csrc/tests/asan_kernel_stubs.cpp \
+    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp
 
 asan-api: $(ASAN_API)
 
@@ -142,7 +143,8 @@ $(TSAN_API): $(ASAN_SRC)
 # Concurrent-submit race test (multi-producer MPSC ring) under TSan.
 TSAN_SUBMIT := $(BUILD)/submit_race_tsan
 TSAN_SUBMIT_SRC := $(CSRC) mlsl_amd/csrc/tests/submit_race_selftest.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs.cpp
+    mlsl_amd/csrc/tests/asan_kernel_stubs.cpp \
+    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp
 
 tsan-submit: $(TSAN_SUBMIT)
 

@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Driver config 5: int8-quantized allreduce of bf16/f32 gradients
 (default 256 MiB) vs the uncompressed path — bandwidth + quantization error.
-Launch with torchrun for N>1."""
+Launch with torchrun for N>1.
+
+--mode sum_dequant_ab: single-GPU A/B of the quantized reduce-scatter's last
+hop — the fused quant_sum_dequant kernel against the sequence it replaces,
+quant_accum followed by dequantize of the same wires (--melems elements,
+block 256, f32 and bf16; interleaved rounds in one process).
+--mode reduce_scatter: quantized against exact reduce-scatter of --melems
+elements per rank (launch with benchmarks/mp_run.py for N>1)."""
 import argparse
 import json
 import os
@@ -11,14 +18,98 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def sum_dequant_ab(args):
+    """One line of JSON per dtype. Every op call ends in a stream
+    synchronise, so each timing is host clock around `iters` launch+sync
+    pairs; `call_overhead_us` is the same loop on one block, i.e. what a
+    call costs beyond its kernel (the old sequence pays it twice)."""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("sum_dequant_ab measures GPU kernels: no GPU found")
+    from mlsl_amd import ops
+    torch.cuda.set_device(0)
+    count, block = args.melems << 20, 256
+    wbytes = ops.wire_bytes(count, block)
+    torch.manual_seed(0)
+    wires = []
+    for mul in (1.0, 7.0):
+        v = torch.randn(count, dtype=torch.float32, device="cuda") * mul
+        wire = torch.empty(wbytes, dtype=torch.uint8, device="cuda")
+        ops.quantize(v, wire, count, block=block, dtype="f32")
+        wires.append(wire)
+        del v
+    a, b = wires
+    acc = a.clone()
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters
+
+    for dtype, tdt, es in (("f32", torch.float32, 4), ("bf16", torch.bfloat16, 2)):
+        out = torch.empty(count, dtype=tdt, device="cuda")
+        variants = {
+            "accum": lambda: ops.quant_accum(acc, b, count, block=block),
+            "dequant": lambda: ops.dequantize(acc, out, count, block=block, dtype=dtype),
+            "accum_then_dequant": lambda: (
+                ops.quant_accum(acc, b, count, block=block),
+                ops.dequantize(acc, out, count, block=block, dtype=dtype)),
+            "fused": lambda: ops.quant_sum_dequant(a, b, out, count, block=block,
+                                                   dtype=dtype),
+            "fused_nt": lambda: ops.quant_sum_dequant_nt(a, b, out, count, block=block,
+                                                         dtype=dtype),
+            "call_overhead": lambda: ops.quant_sum_dequant(a, b, out, block, block=block,
+                                                           dtype=dtype),
+        }
+        for fn in variants.values():       # warm-up: every shape that is timed
+            for _ in range(args.warmup):
+                fn()
+        times = {k: [] for k in variants}
+        for _ in range(args.rounds):       # interleaved rounds
+            for k, fn in variants.items():
+                times[k].append(timed(fn))
+        res = {"config": "quant-sum-dequant-ab", "dtype": dtype,
+               "melems": args.melems, "block": block, "iters": args.iters,
+               "rounds": args.rounds}
+        for k, v in times.items():
+            res[f"{k}_us_median"] = round(_median(v) * 1e6, 1)
+            res[f"{k}_us_min"] = round(min(v) * 1e6, 1)
+        # bytes the fused kernel has to move: two payload bytes in (+headers),
+        # one element out
+        fused_bytes = 2 * wbytes + count * es
+        res["fused_TBps"] = round(fused_bytes / _median(times["fused"]) / 1e12, 3)
+        res["fused_over_old"] = round(_median(times["fused"]) /
+                                      _median(times["accum_then_dequant"]), 3)
+        res["fused_nt_over_fused"] = round(_median(times["fused_nt"]) /
+                                           _median(times["fused"]), 3)
+        print(json.dumps(res), flush=True)
+        del out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", default="allreduce",
+                    choices=["allreduce", "reduce_scatter", "sum_dequant_ab"])
+    ap.add_argument("--melems", type=int, default=64,
+                    help="Mi elements (per rank) for the two reduce-scatter modes")
+    ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mbytes", type=int, default=256)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--device", default="auto")
     args = ap.parse_args()
+    if args.mode == "sum_dequant_ab":
+        return sum_dequant_ab(args)
+    rs = args.mode == "reduce_scatter"
 
     use_cuda = False
     torch = None
@@ -37,6 +128,9 @@ def main():
     rank, size = mx.rank(), mx.world_size()
     es = 2 if args.dtype == "bf16" else 4
     count = args.mbytes * 1024 * 1024 // es
+    if rs:
+        # `count` stays the send buffer's length; every rank receives 1/size
+        count = (args.melems << 20) // size * size
 
     if use_cuda:
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)) %
@@ -58,10 +152,13 @@ def main():
         out_x = np.empty_like(g)
 
     d = mx.Distribution(size, 1)
-    qreq = mx.PersistentRequest(d, "all_reduce", count, dtype=args.dtype,
+    kind, req_count = ("reduce_scatter", count // size) if rs else ("all_reduce", count)
+    qreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype,
                                 op="sum", group="data", quantized=True)
-    xreq = mx.PersistentRequest(d, "all_reduce", count, dtype=args.dtype,
+    xreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype,
                                 op="sum", group="data")
+    if rs:
+        out_q, out_x = out_q[:req_count], out_x[:req_count]
 
     def sync():
         if use_cuda:
@@ -96,9 +193,10 @@ def main():
 
     if rank == 0:
         print(json.dumps({
-            "config": "int8-quantized-allreduce",
+            "config": "int8-quantized-reduce-scatter" if rs
+                      else "int8-quantized-allreduce",
             "dtype": args.dtype,
-            "message_mib": args.mbytes,
+            "message_mib": count * es >> 20,
             "world": size,
             **{f"{k}_{kk}": vv for k, v in results.items() for kk, vv in v.items()},
             "wire_compression": round(es / ((256 + 8) / 256), 2),

@@ -392,6 +392,8 @@ class PersistentRequest:
                                                      c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_reduce_scatter.argtypes = [c_void_p, c_size_t, c_int,
                                                          c_int, c_int, P(c_void_p)]
+            L.mlsl_persistent_reduce_scatter_quantized.argtypes = [
+                c_void_p, c_size_t, c_int, c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_all_gather.argtypes = [c_void_p, c_size_t, c_int, c_int,
                                                      P(c_void_p)]
             L.mlsl_persistent_all_to_all.argtypes = [c_void_p, c_size_t, c_int, c_int,
@@ -401,6 +403,7 @@ class PersistentRequest:
             L.mlsl_request_test.argtypes = [c_void_p, P(c_int)]
             L.mlsl_request_destroy.argtypes = [c_void_p]
             for n in ("mlsl_persistent_all_reduce", "mlsl_persistent_reduce_scatter",
+                      "mlsl_persistent_reduce_scatter_quantized",
                       "mlsl_persistent_all_gather", "mlsl_persistent_all_to_all",
                       "mlsl_request_start", "mlsl_request_wait", "mlsl_request_test",
                       "mlsl_request_destroy"):
@@ -412,9 +415,12 @@ class PersistentRequest:
                                                GROUP[group], 1 if quantized else 0,
                                                ctypes.byref(h)))
         elif kind == "reduce_scatter":
-            check(L.mlsl_persistent_reduce_scatter(dist._h, count, DTYPE[dtype],
-                                                   REDOP[op], GROUP[group],
-                                                   ctypes.byref(h)))
+            # int8 wire with error feedback; raises for anything but a sum
+            # of f32/bf16 rather than running the exact collective instead
+            fn = (L.mlsl_persistent_reduce_scatter_quantized if quantized
+                  else L.mlsl_persistent_reduce_scatter)
+            check(fn(dist._h, count, DTYPE[dtype], REDOP[op], GROUP[group],
+                     ctypes.byref(h)))
         elif kind == "all_gather":
             check(L.mlsl_persistent_all_gather(dist._h, count, DTYPE[dtype],
                                                GROUP[group], ctypes.byref(h)))

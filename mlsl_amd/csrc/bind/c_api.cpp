@@ -5,6 +5,7 @@
 #include "../include/mlsl/c_api.h"
 
 #include <cstring>
+#include <memory>
 #include <string>
 
 #include "../comm/group.hpp"
@@ -253,6 +254,24 @@ int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
     r->AddReduceScatter(recv_count, ROP(op));
     r->Setup();
     *out = r;
+    C_CATCH
+}
+
+int mlsl_persistent_reduce_scatter_quantized(mlsl_distribution d, size_t recv_count,
+                                             mlsl_data_type dt, mlsl_reduction op,
+                                             mlsl_group g, mlsl_request* out) {
+    C_TRY
+    // never fall back to an exact reduce-scatter behind the caller's back
+    MLSL_CHECK(ROP(op) == ReduceOp::SUM,
+               "quantized reduce_scatter supports the SUM reduction only");
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized reduce_scatter supports f32/bf16 only");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddReduceScatter(recv_count, ROP(op));
+    r->SetCompression(Compression::QUANT_INT8,
+                      Environment::GetEnv().GetQuantizationParams());
+    r->Setup();
+    *out = r.release();
     C_CATCH
 }
 

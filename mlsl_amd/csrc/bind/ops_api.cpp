@@ -114,6 +114,22 @@ int mlsl_hip_quant_accum(void* acc, const void* wire, size_t count, size_t block
     OPS_CATCH
 }
 
+int mlsl_hip_quant_sum_dequant(const void* a_wire, const void* b_wire, void* out,
+                               size_t count, size_t block, int dt) {
+    OPS_TRY LaunchQuantSumDequant(a_wire, b_wire, out, count, block,
+                                  static_cast<DataType>(dt), nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_quant_sum_dequant_nt(const void* a_wire, const void* b_wire, void* out,
+                                  size_t count, size_t block, int dt) {
+    OPS_TRY LaunchQuantSumDequantNT(a_wire, b_wire, out, count, block,
+                                    static_cast<DataType>(dt), nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
 // Host codec (comm/quant.cpp) on host pointers: same wire format and the
 // same argument order as the device ops above.
 int mlsl_host_quantize(const void* in, void* err, void* wire, size_t count,
@@ -132,6 +148,13 @@ int mlsl_host_dequantize(const void* wire, void* out, size_t count, size_t block
 int mlsl_host_quant_accum(void* acc, const void* wire, size_t count, size_t block) {
     OPS_TRY CheckQuantBlock(block, "mlsl_host_quant_accum");
     HostQuantAccum(acc, wire, count, block);
+    OPS_CATCH
+}
+
+int mlsl_host_quant_sum_dequant(const void* a_wire, const void* b_wire, void* out,
+                                size_t count, size_t block, int dt) {
+    OPS_TRY HostQuantSumDequant(a_wire, b_wire, out, count, block,
+                                static_cast<DataType>(dt));
     OPS_CATCH
 }
 

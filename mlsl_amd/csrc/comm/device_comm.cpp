@@ -326,15 +326,77 @@ DeviceRuntime* CreateDeviceRuntime() {
     return rt;
 }
 
+namespace {
+
+// Scratch of one compressed chunk: [wire][schedule scratch][residual].
+// Each region is 16-B aligned so the vectorized quant kernels' fast paths
+// apply (wire blocks are 264 B, so raw offsets are only 8-B aligned).
+struct QuantScratch {
+    uint8_t* wire;
+    uint8_t* scratch;
+    uint8_t* err;
+    size_t bytes;  // all three regions
+};
+
+// `base` may be null when only the size is wanted.
+QuantScratch QuantLayout(CommRequest* req, const ChunkExec& ce, uint8_t* base) {
+    auto al16 = [](size_t x) { return (x + 15) & ~size_t(15); };
+    const size_t wire_b = al16(req->WireBytesFor(ce));
+    const size_t scratch_b = al16(ce.sch.tmp_bytes);
+    QuantScratch q{};
+    q.bytes = wire_b + scratch_b +
+              al16(req->ResidualElems() * DtypeSize(req->Dtype()));
+    if (base) {
+        q.wire = base;
+        q.scratch = base + wire_b;
+        q.err = base + wire_b + scratch_b;
+    }
+    return q;
+}
+
+// Reduce-scatter quantizes each of its N send segments on a block grid of
+// its own, residual alongside; the allreduce is one segment. The whole send
+// buffer is on the wire before anything writes the recv buffer, so the two
+// may alias anywhere.
+void QuantPrologue(CommRequest* req, const ChunkExec& ce, const QuantScratch& q,
+                   const uint8_t* sbuf, hipStream_t s) {
+    const OpSpec& spec = req->Spec();
+    const size_t nseg = spec.op == CollOp::REDUCE_SCATTER
+                            ? static_cast<size_t>(req->Group()->Size()) : 1;
+    const size_t seg_b = spec.count * DtypeSize(req->Dtype());
+    const size_t seg_wire = req->WireBytesFor(ce) / nseg;
+    for (size_t j = 0; j < nseg; ++j)
+        LaunchQuantize(sbuf + j * seg_b, q.err + j * seg_b, q.wire + j * seg_wire,
+                       spec.count, req->QParams().block_elems, req->Dtype(), true, s);
+}
+
+// Allreduce (and any op on a group of one): dequantize the result wire.
+// Reduce-scatter: the partial sum that arrived last sits in its TMP slot;
+// one fused kernel adds this rank's own wire segment and writes elements.
+void QuantEpilogue(CommRequest* req, const ChunkExec& ce, const QuantScratch& q,
+                   uint8_t* rbuf, hipStream_t s) {
+    const OpSpec& spec = req->Spec();
+    const size_t blk = req->QParams().block_elems;
+    const BufRef& res = ce.sch.result;
+    if (res.space == Space::TMP) {
+        const size_t n = static_cast<size_t>(req->Group()->Size());
+        const uint8_t* own = q.wire + static_cast<size_t>(req->Group()->MyIdx()) *
+                                          (req->WireBytesFor(ce) / n);
+        LaunchQuantSumDequant(q.scratch + res.off, own, rbuf, spec.count, blk,
+                              req->Dtype(), s);
+    } else {
+        LaunchDequantize(q.wire + res.off, rbuf, spec.count, blk, req->Dtype(), s);
+    }
+}
+
+}  // namespace
+
 void DeviceSetupRequest(CommRequest* req, DeviceReqState& st) {
     // Persistent scratch only where the device executor needs it: the
     // compressed path (wire + residual), the custom schedule path (segment
     // staging), and the barrier token. The fused RCCL path allocates
     // nothing — one-shot hot-loop requests must not pay a hipMalloc+memset
     // per iteration.
-    // 16-B-align each region so the vectorized quant kernels' fast paths
-    // apply (wire blocks are 264 B, so raw offsets are only 8-B aligned).
-    auto al16 = [](size_t x) { return (x + 15) & ~size_t(15); };
     size_t tmp = 0;
     if (req->Compressed()) {
         // The dlopen'd compression plugin is a host-CPU contract
@@ -345,8 +407,7 @@ void DeviceSetupRequest(CommRequest* req, DeviceReqState& st) {
                    "transport only; device mode uses the built-in CDNA4 "
                    "kernels (unset lib_path)");
         for (auto& ce : req->Chunks())
-            tmp += al16(ce.sch.result.bytes) + al16(ce.sch.tmp_bytes) +
-                   al16(req->Spec().count * DtypeSize(req->Dtype()));
+            tmp += QuantLayout(req, ce, nullptr).bytes;
     } else if (req->UsesDeviceSchedule()) {
         for (auto& ce : req->Chunks()) tmp += ce.sch.tmp_bytes;
     }
@@ -893,16 +954,12 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st) {
                 const uint8_t* sbase = req->SendBuf() + ce.elem_off * es;
                 uint8_t* rbase = req->RecvBuf() + ce.elem_off * es;
                 if (compressed) {
-                    // quantize -> dequantize keeps quantized-allreduce
-                    // semantics (and error feedback) at n=1
-                    uint8_t* wire = static_cast<uint8_t*>(st.tmp_dev);
-                    uint8_t* err = wire + ((ce.sch.result.bytes + 15) & ~size_t(15)) +
-                                   ((ce.sch.tmp_bytes + 15) & ~size_t(15));
-                    const size_t blk = req->QParams().block_elems;
-                    LaunchQuantize(sbase, err, wire, req->Spec().count, blk,
-                                   req->Dtype(), true, s0);
-                    LaunchDequantize(wire, rbase, req->Spec().count, blk,
-                                     req->Dtype(), s0);
+                    // quantize -> dequantize keeps the quantized
+                    // collective's semantics (and error feedback) at n=1
+                    const QuantScratch q =
+                        QuantLayout(req, ce, static_cast<uint8_t*>(st.tmp_dev));
+                    QuantPrologue(req, ce, q, sbase, s0);
+                    QuantEpilogue(req, ce, q, rbase, s0);
                 } else if (ce.sch.result.bytes && sbase != rbase) {
                     // NT copy kernel: measured faster than the blit path for
                     // large streams (docs/BENCHMARKS.md); buffers are device
@@ -928,19 +985,12 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st) {
                 const size_t lane = prio ? gc.p2p->Lanes() - 1 : ch;
                 uint8_t* tbase = static_cast<uint8_t*>(st.tmp_dev) + tmp_off;
                 if (compressed) {
-                    const size_t wire_b = (ce.sch.result.bytes + 15) & ~size_t(15);
-                    uint8_t* wire = tbase;
-                    uint8_t* scratch = tbase + wire_b;
-                    uint8_t* err = scratch + ((ce.sch.tmp_bytes + 15) & ~size_t(15));
-                    const size_t blk = req->QParams().block_elems;
-                    LaunchQuantize(req->SendBuf(), err, wire, req->Spec().count,
-                                   blk, req->Dtype(), true, strm_);
-                    gc.p2p->IssueSchedule(req, ce, lane, strm_, wire, wire,
-                                          scratch);
-                    LaunchDequantize(wire, req->RecvBuf(), req->Spec().count,
-                                     blk, req->Dtype(), strm_);
-                    tmp_off += wire_b + ((ce.sch.tmp_bytes + 15) & ~size_t(15)) +
-                               ((req->Spec().count * es + 15) & ~size_t(15));
+                    const QuantScratch q = QuantLayout(req, ce, tbase);
+                    QuantPrologue(req, ce, q, req->SendBuf(), strm_);
+                    gc.p2p->IssueSchedule(req, ce, lane, strm_, q.wire, q.wire,
+                                          q.scratch);
+                    QuantEpilogue(req, ce, q, req->RecvBuf(), strm_);
+                    tmp_off += q.bytes;
                 } else {
                     gc.p2p->IssueSchedule(req, ce, lane, strm_,
                                           req->SendBuf() + ce.elem_off * es,
@@ -954,19 +1004,12 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st) {
             uint8_t* tbase = static_cast<uint8_t*>(st.tmp_dev) + tmp_off;
             if (compressed) {
                 // quantize -> compressed-domain ring -> dequantize (driver
-                // config 5: int8 allreduce of bf16/f32 grads)
-                const size_t wire_b = (ce.sch.result.bytes + 15) & ~size_t(15);
-                uint8_t* wire = tbase;
-                uint8_t* scratch = tbase + wire_b;
-                uint8_t* err = scratch + ((ce.sch.tmp_bytes + 15) & ~size_t(15));
-                const size_t blk = req->QParams().block_elems;
-                LaunchQuantize(req->SendBuf(), err, wire, req->Spec().count, blk,
-                               req->Dtype(), true, strm_);
-                IssueSchedule(req, ce, comm_, strm_, wire, wire, scratch);
-                LaunchDequantize(wire, req->RecvBuf(), req->Spec().count, blk,
-                                 req->Dtype(), strm_);
-                tmp_off += wire_b + ((ce.sch.tmp_bytes + 15) & ~size_t(15)) +
-                           ((req->Spec().count * es + 15) & ~size_t(15));
+                // config 5: int8 allreduce / reduce-scatter of bf16/f32 grads)
+                const QuantScratch q = QuantLayout(req, ce, tbase);
+                QuantPrologue(req, ce, q, req->SendBuf(), strm_);
+                IssueSchedule(req, ce, comm_, strm_, q.wire, q.wire, q.scratch);
+                QuantEpilogue(req, ce, q, req->RecvBuf(), strm_);
+                tmp_off += q.bytes;
             } else if (use_schedule) {
                 IssueSchedule(req, ce, comm_, strm_,
                               req->SendBuf() + ce.elem_off * es,

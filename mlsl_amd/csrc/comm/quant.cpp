@@ -128,6 +128,33 @@ void HostQuantAccum(void* acc_wire, const void* wire, size_t count, size_t block
     }
 }
 
+void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
+                         size_t count, size_t block, DataType dt) {
+    CheckQuantBlock(block, "HostQuantSumDequant");
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW("quantized sum-dequantize supports f32/bf16 only");
+    const size_t nblocks = (count + block - 1) / block;
+    const uint8_t* aw = static_cast<const uint8_t*>(a_wire);
+    const uint8_t* bw = static_cast<const uint8_t*>(b_wire);
+    for (size_t blk = 0; blk < nblocks; ++blk) {
+        const size_t base = blk * block;
+        const size_t n = std::min(block, count - base);
+        const uint8_t* ab = aw + blk * (block + 8);
+        const uint8_t* bb = bw + blk * (block + 8);
+        const float as = reinterpret_cast<const float*>(ab)[0];
+        const float bs = reinterpret_cast<const float*>(bb)[0];
+        const int8_t* ap = reinterpret_cast<const int8_t*>(ab + 8);
+        const int8_t* bp = reinterpret_cast<const int8_t*>(bb + 8);
+        if (dt == DataType::F32) {
+            float* o = static_cast<float*>(out);
+            for (size_t i = 0; i < n; ++i) o[base + i] = ap[i] * as + bp[i] * bs;
+        } else {
+            uint16_t* o = static_cast<uint16_t*>(out);
+            for (size_t i = 0; i < n; ++i) o[base + i] = F32B(ap[i] * as + bp[i] * bs);
+        }
+    }
+}
+
 const QuantPluginApi* LoadQuantPlugin(const QuantParams& qp) {
     if (qp.lib_path.empty()) return nullptr;
     static std::mutex mu;

@@ -25,6 +25,10 @@ void HostDequantize(const void* wire, void* out, size_t count, size_t block,
                     DataType dt);
 // acc_wire += wire in the compressed domain (dequant-sum-requant per block).
 void HostQuantAccum(void* acc_wire, const void* wire, size_t count, size_t block);
+// out = dequant(a_wire) + dequant(b_wire) in the element type, wires
+// untouched: the quantized reduce-scatter's last hop (no requantization).
+void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
+                         size_t count, size_t block, DataType dt);
 
 // dlopen'd compression plugin (reference quant/quant.c ABI — Intel
 // DL-comp style). Loaded once per lib_path; used by the HOST compressed

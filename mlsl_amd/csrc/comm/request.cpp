@@ -35,7 +35,9 @@ const char* CollOpName(CollOp op) {
 
 void ChunkExec::Reset() {
     cur_phase = sch.steps.empty() ? sch.num_phases : 0;
-    finished = sch.num_phases == 0;
+    // a compressed chunk still has its quantize/dequantize to run when its
+    // schedule is empty (quantized reduce-scatter on a group of one)
+    finished = sch.num_phases == 0 && sch.quant_block == 0;
     prologue_done = false;
     state.assign(sch.steps.size(), StepState{});
 }
@@ -142,7 +144,8 @@ void CommRequest::SetCompression(Compression c, const QuantParams& qp) {
 }
 
 bool CommRequest::Compressed() const {
-    return comp_ == Compression::QUANT_INT8 && spec_.op == CollOp::ALLREDUCE &&
+    return comp_ == Compression::QUANT_INT8 &&
+           (spec_.op == CollOp::ALLREDUCE || spec_.op == CollOp::REDUCE_SCATTER) &&
            (dtype_ == DataType::F32 || dtype_ == DataType::BF16) &&
            spec_.rop == ReduceOp::SUM;
 }
@@ -162,8 +165,13 @@ bool CommRequest::UsesDeviceSchedule() const {
 }
 
 size_t CommRequest::WireBytesFor(const ChunkExec& ce) const {
-    // compressed chunks: Schedule::result is already in wire bytes
-    return ce.sch.result.bytes;
+    return ce.sch.wire_bytes;
+}
+
+size_t CommRequest::ResidualElems() const {
+    return spec_.op == CollOp::REDUCE_SCATTER
+               ? spec_.count * static_cast<size_t>(group_->Size())
+               : spec_.count;
 }
 
 size_t CommRequest::MessageBytes() const {
@@ -302,7 +310,15 @@ void CommRequest::BuildChunks() {
                 ce.sch = BuildBcast(gr, gs, cnt, dtype_, spec_.root);
                 break;
             case CollOp::REDUCE_SCATTER:
-                if (n_chunks > 1) {
+                if (Compressed()) {
+                    // Quantized reduce-scatter: every send segment is its
+                    // own run of wire blocks, the ring accumulates in the
+                    // compressed domain, and the last hop is the fused
+                    // sum-dequantize epilogue. Single chunk.
+                    const size_t blk = qparams_.block_elems;
+                    ce.sch = BuildReduceScatterUnits(gr, gs, (spec_.count + blk - 1) / blk,
+                                                     qparams_.WireBlockBytes(), blk);
+                } else if (n_chunks > 1) {
                     ce.elem_off = 0;  // chunk offsets are absolute
                     ce.sch = BuildReduceScatterChunk(
                         gr, gs, spec_.count, SegOffset(spec_.count, n_chunks, c),
@@ -388,8 +404,8 @@ void CommRequest::Setup() {
             size_t t = ce.sch.tmp_bytes;
             if (Compressed()) {
                 // [wire][schedule scratch][error-feedback residual]
-                const size_t wire = ce.sch.result.bytes;
-                const size_t err = spec_.count * DtypeSize(dtype_);
+                const size_t wire = WireBytesFor(ce);
+                const size_t err = ResidualElems() * DtypeSize(dtype_);
                 t = wire + ce.sch.tmp_bytes + err;
             }
             ce.tmp.assign(t, 0);
@@ -531,7 +547,12 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
         const uint8_t* sbase = sbuf_ + ce.elem_off * es;
         uint8_t* rbase = rbuf_ + ce.elem_off * es;
         uint8_t* wire = ce.tmp.data();                         // compressed only
-        const size_t wire_bytes = compressed ? ce.sch.result.bytes : 0;
+        const size_t wire_bytes = compressed ? WireBytesFor(ce) : 0;
+        // Reduce-scatter quantizes each of its N send segments on a block
+        // grid of its own; the allreduce is one segment.
+        const size_t nseg = spec_.op == CollOp::REDUCE_SCATTER
+                                ? static_cast<size_t>(group_->Size()) : 1;
+        const size_t seg_wire = wire_bytes / nseg;
         auto ptr = [&](const BufRef& b) -> uint8_t* {
             if (compressed) {
                 switch (b.space) {
@@ -549,19 +570,25 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
         };
         if (compressed && !ce.prologue_done) {
             // quantize user send (+ residual) into the wire
+            // The whole send buffer is quantized before the first byte of
+            // the recv buffer is written, so the two may alias anywhere.
             uint8_t* err = ce.tmp.data() + wire_bytes + ce.sch.tmp_bytes;
-            if (plugin_) {
-                // reference ABI: dtype enum {INT8=0,F16=1,F32=2,F64=3},
-                // comp_ratio = input-elem-bytes (int8 wire), method DFP=1
-                const int sdt = dtype_ == DataType::F32 ? 2
-                                : dtype_ == DataType::F64 ? 3 : 1;
-                int rc = plugin_->quant(const_cast<uint8_t*>(sbase), wire,
-                                        spec_.count, err, sdt,
-                                        DtypeSize(dtype_), 1);
-                MLSL_CHECK(rc == 0, "quant plugin compress failed");
-            } else {
-                HostQuantize(sbase, err, wire, spec_.count, qparams_.block_elems,
-                             dtype_, true);
+            for (size_t j = 0; j < nseg; ++j) {
+                const uint8_t* seg = sbase + j * spec_.count * es;
+                uint8_t* seg_err = err + j * spec_.count * es;
+                if (plugin_) {
+                    // reference ABI: dtype enum {INT8=0,F16=1,F32=2,F64=3},
+                    // comp_ratio = input-elem-bytes (int8 wire), method DFP=1
+                    const int sdt = dtype_ == DataType::F32 ? 2
+                                    : dtype_ == DataType::F64 ? 3 : 1;
+                    int rc = plugin_->quant(const_cast<uint8_t*>(seg),
+                                            wire + j * seg_wire, spec_.count,
+                                            seg_err, sdt, DtypeSize(dtype_), 1);
+                    MLSL_CHECK(rc == 0, "quant plugin compress failed");
+                } else {
+                    HostQuantize(seg, seg_err, wire + j * seg_wire, spec_.count,
+                                 qparams_.block_elems, dtype_, true);
+                }
             }
             ce.prologue_done = true;
         }
@@ -629,11 +656,26 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
             if (ce.cur_phase >= ce.sch.num_phases) {
                 ce.finished = true;
                 if (compressed) {
+                    // Reduce-scatter on more than one rank: the partial sum
+                    // that arrived last and this rank's own wire segment
+                    // still have to meet. The plugin ABI has no fused hook,
+                    // so there the sum is requantized into the arrival slot.
+                    uint8_t* res = ptr(ce.sch.result);
+                    const uint8_t* own =
+                        nseg > 1 ? wire + static_cast<size_t>(group_->MyIdx()) * seg_wire
+                                 : nullptr;
                     if (plugin_) {
-                        int rc = plugin_->dequant(wire, rbase, spec_.count);
+                        int rc = own ? plugin_->reduce_sum(
+                                           own, res, seg_wire / qparams_.WireBlockBytes())
+                                     : 0;
+                        MLSL_CHECK(rc == 0, "quant plugin reduce failed");
+                        rc = plugin_->dequant(res, rbase, spec_.count);
                         MLSL_CHECK(rc == 0, "quant plugin decompress failed");
+                    } else if (own) {
+                        HostQuantSumDequant(res, own, rbase, spec_.count,
+                                            qparams_.block_elems, dtype_);
                     } else {
-                        HostDequantize(wire, rbase, spec_.count,
+                        HostDequantize(res, rbase, spec_.count,
                                        qparams_.block_elems, dtype_);
                     }
                 }

@@ -105,8 +105,9 @@ class CommRequest {
     void AddBarrier();
     void AddSendRecvList(const std::vector<SRPair>& pairs);
     // Gradient compression (reference quant/quant.c contract): int8 block
-    // quantization with error feedback, fused into the allreduce. Call
-    // before Setup(); honored for ALLREDUCE on f32/bf16.
+    // quantization with error feedback, fused into the collective. Call
+    // before Setup(); honored for ALLREDUCE and REDUCE_SCATTER with SUM on
+    // f32/bf16.
     void SetCompression(Compression c, const QuantParams& qp);
     Compression GetCompression() const { return comp_; }
     const QuantParams& QParams() const { return qparams_; }
@@ -116,8 +117,11 @@ class CommRequest {
     // over ncclSend/Recv) instead of the fused RCCL op.
     bool UsesDeviceSchedule() const;
     // Compressed-path layout inside each chunk's tmp:
-    // [wire W][schedule scratch][error-feedback residual].
+    // [wire W][schedule scratch][error-feedback residual]. The wire is the
+    // quantized image of the whole send buffer; the residual has one element
+    // per send element (N * count for REDUCE_SCATTER).
     size_t WireBytesFor(const ChunkExec& ce) const;
+    size_t ResidualElems() const;
 
     // ---- lifecycle ----
     void Setup();                         // compile schedules, size scratch

@@ -154,6 +154,7 @@ Schedule BuildAllReduceRingUnits(int rank, int size, size_t units, size_t unit_b
     Schedule sch = RingAllReduceImpl(rank, size, units, unit_bytes, DataType::U8,
                                      ReduceOp::SUM, 1);
     sch.quant_block = quant_block;
+    sch.wire_bytes = units * unit_bytes;
     return sch;
 }
 
@@ -298,6 +299,43 @@ Schedule BuildReduceScatter(int rank, int size, size_t recv_count, DataType dt, 
     sch.AddStep(MakeCopy(N - 1, Ref(Space::TMP, ((N - 2) % 2) * segB, segB),
                          Ref(Space::RECV, 0, segB)));
     sch.result = Ref(Space::RECV, 0, segB);
+    return sch;
+}
+
+Schedule BuildReduceScatterUnits(int rank, int size, size_t units_per_rank,
+                                 size_t unit_bytes, size_t quant_block) {
+    const size_t segB = units_per_rank * unit_bytes;
+    Schedule sch;
+    sch.dtype = DataType::U8;
+    sch.rop = ReduceOp::SUM;
+    sch.quant_block = quant_block;
+    sch.wire_bytes = static_cast<size_t>(size) * segB;
+    if (size == 1) {
+        sch.result = Ref(Space::SEND, 0, segB);
+        return sch;
+    }
+    const int N = size, r = rank;
+    const int next = (r + 1) % N, prev = (r - 1 + N) % N;
+    const int slots = std::min(2, N - 1);
+    sch.tmp_bytes = static_cast<size_t>(slots) * segB;
+    for (int p = 0; p <= N - 2; ++p) {
+        const int ssend = (r - p - 1 + 2 * N) % N;
+        const int srecv = (r - p - 2 + 2 * N) % N;
+        Step st;
+        st.phase = p;
+        st.send_peer = next;
+        st.send = (p == 0) ? Ref(Space::SEND, ssend * segB, segB)
+                           : Ref(Space::TMP, ((p - 1) % 2) * segB, segB);
+        st.recv_peer = prev;
+        st.recv = Ref(Space::TMP, (p % 2) * segB, segB);
+        if (p < N - 2) {
+            st.local = Step::LocalOp::REDUCE;
+            st.local_src = Ref(Space::SEND, srecv * segB, segB);
+            st.local_dst = st.recv;
+        }
+        sch.AddStep(st);
+    }
+    sch.result = Ref(Space::TMP, ((N - 2) % 2) * segB, segB);
     return sch;
 }
 

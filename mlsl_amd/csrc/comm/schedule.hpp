@@ -59,6 +59,11 @@ struct Schedule {
     // (QuantAccum) over wire blocks of this many elements; buffer refs are
     // then in wire bytes (unit = quant_block + 8).
     size_t quant_block = 0;
+    // quant_block > 0: bytes of the wire image of the user's send buffer,
+    // which the executor keeps in front of the schedule scratch and which
+    // SEND/RECV refs address. Equals result.bytes for the allreduce; the
+    // reduce-scatter's wire holds N segments and its result only one.
+    size_t wire_bytes = 0;
     // Direct (one-shot) allreduce shape: phase 1 is "send TMP(0,B) to all
     // peers, receive each peer's TMP slot, reduce all into RECV(0,B)" —
     // executors may batch it into fan-out/fan-in kernels.
@@ -92,6 +97,14 @@ int RingStrideForChannel(size_t channel, int size);
 // unit = one int8 wire block of quant_block elements + 8-byte header).
 Schedule BuildAllReduceRingUnits(int rank, int size, size_t units, size_t unit_bytes,
                                  size_t quant_block);
+// Ring reduce-scatter over opaque wire units (quantized path): segment j of
+// the wire is units_per_rank units at SEND offset j * units_per_rank *
+// unit_bytes. BuildReduceScatter's shape, except that the last exchange
+// carries no local op and nothing is copied to RECV: the arrived partial sum
+// of this rank's segment stays in the TMP slot that `result` names, for the
+// executor's fused sum-dequantize epilogue. size == 1 has no traffic.
+Schedule BuildReduceScatterUnits(int rank, int size, size_t units_per_rank,
+                                 size_t unit_bytes, size_t quant_block);
 Schedule BuildAllReduceRHD(int rank, int size, size_t count, DataType dt, ReduceOp op);
 // One-shot exchange + local reduce (latency-optimal on full-mesh xGMI;
 // (N-1)x wire cost — small messages only).

@@ -682,6 +682,84 @@ __global__ void QuantAccumKernel(uint8_t* __restrict__ acc,
     QuantAccumBody(acc, in, count, block_elems);
 }
 
+// out = dequant(a) + dequant(b) in the element type: the last hop of the
+// quantized reduce-scatter. The sum is never requantized, so the final rank
+// saves one lossy step and one pass over the wire (accumulate + dequantize).
+// Both wires are local by now (the arrived one was copied out of its
+// hand-off slot), so plain loads. Stores are plain here; the fast path below
+// turns nontemporal for outputs too large to stay cached.
+template <typename T>
+__global__ void QuantSumDequantKernel(const uint8_t* __restrict__ a,
+                                      const uint8_t* __restrict__ b,
+                                      T* __restrict__ out, size_t count,
+                                      size_t block_elems) {
+    // 16-B (f32) / 8-B (bf16) stores need a 16-B-aligned output base
+    const bool vec4 = (block_elems & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    ForEachWaveBlock((count + block_elems - 1) / block_elems, [&](size_t blk, int lane) {
+        const size_t base = blk * block_elems;
+        const size_t n = min(block_elems, count - base);
+        const uint8_t* ablock = a + blk * (block_elems + kWireHdr);
+        const uint8_t* bblock = b + blk * (block_elems + kWireHdr);
+        const float as = WireScale(ablock), bs = WireScale(bblock);
+        const int8_t* ap = reinterpret_cast<const int8_t*>(ablock + kWireHdr);
+        const int8_t* bp = reinterpret_cast<const int8_t*>(bblock + kWireHdr);
+        ForEachBlockElem(n, vec4, lane, [&](size_t i, auto w) {
+            constexpr int W = decltype(w)::value;
+            const int32_t pa = QLoad<W>(ap, i), pb = QLoad<W>(bp, i);
+            if constexpr (W == 4) {
+                std::conditional_t<sizeof(T) == 4, float4_ev, ushort4_t> v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = Encode<T>(QSum(pa, as, pb, bs, j));
+                StoreVec<false>(v, out + base + i);
+            } else {
+                out[base + i] = Encode<T>(QSum(pa, as, pb, bs, 0));
+            }
+        });
+    });
+}
+
+// Fast path (block_elems == 256, whole blocks): two blocks per wave as in
+// the dequantize kernels. bf16 takes 8 consecutive elements per lane (one
+// 16-B store); f32 takes the split-half layout of DequantizeF32x2Kernel so
+// that each of its two 16-B stores is contiguous across the half-wave.
+// NT_ST stores `out` nontemporally (size rule and A/B in the launcher).
+template <typename T, bool NT_ST>
+__global__ void QuantSumDequantX2Kernel(const uint8_t* __restrict__ a,
+                                        const uint8_t* __restrict__ b,
+                                        T* __restrict__ out, size_t nblocks) {
+    ForEachHalfWaveBlock(nblocks, [&](size_t blk, int sub) {
+        const uint8_t* ablock = a + blk * (kFastBlock + kWireHdr);
+        const uint8_t* bblock = b + blk * (kFastBlock + kWireHdr);
+        const float as = WireScale(ablock), bs = WireScale(bblock);
+        T* obase = out + blk * kFastBlock;
+        float o[8];
+        if constexpr (sizeof(T) == 4) {
+            const int32_t* a4 = reinterpret_cast<const int32_t*>(ablock + kWireHdr);
+            const int32_t* b4 = reinterpret_cast<const int32_t*>(bblock + kWireHdr);
+            const int32_t pa0 = a4[sub], pa1 = a4[32 + sub];
+            const int32_t pb0 = b4[sub], pb1 = b4[32 + sub];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = QSum(pa0, as, pb0, bs, j);
+                o[4 + j] = QSum(pa1, as, pb1, bs, j);
+            }
+            StoreVec<NT_ST>(float4_ev{o[0], o[1], o[2], o[3]}, obase + sub * 4);
+            StoreVec<NT_ST>(float4_ev{o[4], o[5], o[6], o[7]}, obase + 128 + sub * 4);
+        } else {
+            const uint2_ev pa =
+                *reinterpret_cast<const uint2_ev*>(ablock + kWireHdr + sub * 8);
+            const uint2_ev pb =
+                *reinterpret_cast<const uint2_ev*>(bblock + kWireHdr + sub * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                o[j] = QSum(static_cast<int32_t>(pa[j >> 2]), as,
+                            static_cast<int32_t>(pb[j >> 2]), bs, j & 3);
+            Store8<NT_ST>(obase + sub * 8, o);
+        }
+    });
+}
+
 inline size_t NumBlocks(size_t count, size_t block_elems) {
     return (count + block_elems - 1) / block_elems;
 }
@@ -809,6 +887,76 @@ void LaunchQuantAccum(void* acc_wire, const void* wire, size_t count,
         QuantAccumKernel<<<WaveGrid(nblocks), dim3(kBlock), 0, stream>>>(a, w, count,
                                                                          block_elems);
     HIP_CHECK(hipGetLastError());
+}
+
+namespace {
+
+// Wires sit at multiples of the 264-B wire block inside a request's scratch
+// (TMP slots, per-rank segments), so they are only 8-B aligned, like the
+// wire of X2Eligible. No size floor: the epilogue has no slower-start
+// generic sibling to beat at small sizes.
+bool SumDequantX2Eligible(size_t count, size_t block_elems, const void* a,
+                          const void* b, const void* out) {
+    return block_elems == kFastBlock && count % kFastBlock == 0 &&
+           (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
+           ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7) == 0;
+}
+
+// Nontemporal stores of `out` from 128 MiB up: measured 95.6 -> 81.9 us at
+// 256 MiB (f32) and 62.9 -> 60.0 us at 128 MiB (bf16); at 64 MiB and below
+// the gain is 0-3 % (docs/BENCHMARKS.md), and plain stores leave a gradient
+// shard of that size in cache for the optimizer that reads it next.
+constexpr size_t kSumDequantNtBytes = size_t(128) << 20;
+
+template <typename T>
+void QuantSumDequantTyped(const void* a_wire, const void* b_wire, void* out,
+                          size_t count, size_t block_elems, bool force_nt,
+                          hipStream_t stream) {
+    const size_t nblocks = NumBlocks(count, block_elems);
+    const uint8_t* a = static_cast<const uint8_t*>(a_wire);
+    const uint8_t* b = static_cast<const uint8_t*>(b_wire);
+    if (SumDequantX2Eligible(count, block_elems, a_wire, b_wire, out))
+        DispatchBool(force_nt || count * sizeof(T) >= kSumDequantNtBytes, [&](auto nt) {
+            QuantSumDequantX2Kernel<T, decltype(nt)::value>
+                <<<PairGrid(nblocks), dim3(kBlock), 0, stream>>>(
+                    a, b, static_cast<T*>(out), nblocks);
+        });
+    else
+        QuantSumDequantKernel<T><<<WaveGrid(nblocks), dim3(kBlock), 0, stream>>>(
+            a, b, static_cast<T*>(out), count, block_elems);
+}
+
+void QuantSumDequantAny(const void* a_wire, const void* b_wire, void* out,
+                        size_t count, size_t block_elems, DataType dt, bool force_nt,
+                        hipStream_t stream, const char* who) {
+    CheckQuantBlock(block_elems, who);
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW("quantized sum-dequantize supports f32/bf16 only");
+    if (count == 0) return;
+    if (dt == DataType::F32)
+        QuantSumDequantTyped<float>(a_wire, b_wire, out, count, block_elems, force_nt,
+                                    stream);
+    else
+        QuantSumDequantTyped<unsigned short>(a_wire, b_wire, out, count, block_elems,
+                                             force_nt, stream);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+void LaunchQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
+                           size_t count, size_t block_elems, DataType dt,
+                           hipStream_t stream) {
+    QuantSumDequantAny(a_wire, b_wire, out, count, block_elems, dt, /*force_nt=*/false,
+                       stream, "LaunchQuantSumDequant");
+}
+
+void LaunchQuantSumDequantNT(const void* a_wire, const void* b_wire, void* out,
+                             size_t count, size_t block_elems, DataType dt,
+                             hipStream_t stream) {
+    // A/B hook: the fast path with nontemporal stores of `out` at any size.
+    QuantSumDequantAny(a_wire, b_wire, out, count, block_elems, dt, /*force_nt=*/true,
+                       stream, "LaunchQuantSumDequantNT");
 }
 
 // ---------------------------------------------------------------------------

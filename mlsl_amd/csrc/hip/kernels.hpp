@@ -49,6 +49,17 @@ void LaunchDequantizeNT(const void* wire, void* out, size_t count,
 // block, matching the reference's reduce_sum plugin hook quant/quant.c:89-94).
 void LaunchQuantAccum(void* acc_wire, const void* wire, size_t count,
                       size_t block_elems, hipStream_t stream);
+// Fused last hop of the quantized reduce-scatter:
+// out[i] = dequant(a_wire)[i] + dequant(b_wire)[i] for i < count, in the
+// element type (fp32/bf16). Neither wire is written; the sum is not
+// requantized. Outputs of 128 MiB and more are stored nontemporally on the
+// fast path; the NT variant does so at any size (A/B hook).
+void LaunchQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
+                           size_t count, size_t block_elems, DataType dt,
+                           hipStream_t stream);
+void LaunchQuantSumDequantNT(const void* a_wire, const void* b_wire, void* out,
+                             size_t count, size_t block_elems, DataType dt,
+                             hipStream_t stream);
 
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,

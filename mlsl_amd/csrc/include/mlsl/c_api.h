@@ -102,6 +102,15 @@ int mlsl_persistent_all_reduce(mlsl_distribution d, size_t count, mlsl_data_type
 int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
                                    mlsl_data_type dt, mlsl_reduction op, mlsl_group g,
                                    mlsl_request* out);
+/* int8-quantized reduce-scatter with error feedback (block size from
+ * mlsl_set_quant_params). Each of the N send segments of recv_count elements
+ * is quantized on its own block grid; the request keeps a residual of
+ * N * recv_count elements across starts. The recv buffer may alias any part
+ * of the send buffer. Fails (see mlsl_last_error) unless op is MLSL_RT_SUM
+ * and dt is f32 or bf16; it never runs an exact reduce-scatter instead. */
+int mlsl_persistent_reduce_scatter_quantized(mlsl_distribution d, size_t recv_count,
+                                             mlsl_data_type dt, mlsl_reduction op,
+                                             mlsl_group g, mlsl_request* out);
 int mlsl_persistent_all_gather(mlsl_distribution d, size_t send_count, mlsl_data_type dt,
                                mlsl_group g, mlsl_request* out);
 int mlsl_persistent_all_to_all(mlsl_distribution d, size_t send_count, mlsl_data_type dt,

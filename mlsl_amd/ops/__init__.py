@@ -35,10 +35,16 @@ def _lib():
         L.mlsl_hip_quantize_f32_nt.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p,
                                                c.c_size_t, c.c_size_t]
         L.mlsl_hip_quant_accum.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t, c.c_size_t]
+        L.mlsl_hip_quant_sum_dequant.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p,
+                                                 c.c_size_t, c.c_size_t, c.c_int]
+        L.mlsl_hip_quant_sum_dequant_nt.argtypes = L.mlsl_hip_quant_sum_dequant.argtypes
+        L.mlsl_host_quant_sum_dequant.argtypes = L.mlsl_hip_quant_sum_dequant.argtypes
         L.mlsl_host_quantize.argtypes = L.mlsl_hip_quantize.argtypes
         L.mlsl_host_dequantize.argtypes = L.mlsl_hip_dequantize.argtypes
         L.mlsl_host_quant_accum.argtypes = L.mlsl_hip_quant_accum.argtypes
-        for n in ("mlsl_host_quantize", "mlsl_host_dequantize", "mlsl_host_quant_accum"):
+        for n in ("mlsl_host_quantize", "mlsl_host_dequantize", "mlsl_host_quant_accum",
+                  "mlsl_hip_quant_sum_dequant", "mlsl_hip_quant_sum_dequant_nt",
+                  "mlsl_host_quant_sum_dequant"):
             getattr(L, n).restype = c.c_int
         ptypes = [c.c_void_p, c.c_void_p] + [c.c_size_t] * 8 + [c.c_int]
         L.mlsl_hip_pack.argtypes = ptypes
@@ -138,6 +144,26 @@ def quant_accum(acc_wire, wire, count, block=256):
     check(_lib().mlsl_hip_quant_accum(ap, wp, count, block))
 
 
+def quant_sum_dequant(a_wire, b_wire, out, count, block=256, dtype=None):
+    """out = dequantize(a_wire) + dequantize(b_wire) in one pass, in the
+    element type of `out` (f32/bf16); the wires are not written. The last hop
+    of the quantized reduce-scatter, which never requantizes the sum."""
+    ap, _ = _as_ptr_dtype(a_wire)
+    bp, _ = _as_ptr_dtype(b_wire)
+    op_, d1 = _as_ptr_dtype(out)
+    dt = dtype or d1
+    check(_lib().mlsl_hip_quant_sum_dequant(ap, bp, op_, count, block, DTYPE[dt]))
+
+
+def quant_sum_dequant_nt(a_wire, b_wire, out, count, block=256, dtype=None):
+    """`quant_sum_dequant` with nontemporal stores (benchmark variant)."""
+    ap, _ = _as_ptr_dtype(a_wire)
+    bp, _ = _as_ptr_dtype(b_wire)
+    op_, d1 = _as_ptr_dtype(out)
+    dt = dtype or d1
+    check(_lib().mlsl_hip_quant_sum_dequant_nt(ap, bp, op_, count, block, DTYPE[dt]))
+
+
 _ELEM_BYTES = {"f32": 4, "bf16": 2}
 
 
@@ -181,6 +207,15 @@ def host_quant_accum(acc_wire, wire, count, block=256):
     ap = _host_buf(acc_wire, wire_bytes(count, block), "acc_wire")
     wp = _host_buf(wire, wire_bytes(count, block), "wire")
     check(_lib().mlsl_host_quant_accum(ap, wp, count, block))
+
+
+def host_quant_sum_dequant(a_wire, b_wire, out, count, block=256, dtype="f32"):
+    """Host twin of `quant_sum_dequant` on numpy arrays."""
+    _check_block(block)
+    ap = _host_buf(a_wire, wire_bytes(count, block), "a_wire")
+    bp = _host_buf(b_wire, wire_bytes(count, block), "b_wire")
+    op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
+    check(_lib().mlsl_host_quant_sum_dequant(ap, bp, op_, count, block, DTYPE[dtype]))
 
 
 def pack(src, dst, *, mb_offset, mb_count, fm_offset, fm_count, fm_size,

@@ -26,6 +26,9 @@ Usage (one process per GPU):
 ``reduce="rs"`` and it replaces the gradient allreduce entirely —
 reduce_scatter(grad) + sharded step + all_gather(param), one exchange of
 each flat buffer per step (the reference's grad RS + increment AG pair).
+With ``compression="int8"`` that reduce_scatter travels as int8 wire blocks
+with error feedback (one persistent request, so the residual carries over
+from step to step); the parameter all_gather stays exact.
 """
 import torch
 
@@ -39,9 +42,13 @@ def _dt(t):
 
 class ShardedOptimizer:
     def __init__(self, params, opt_cls, dist=None, group="data",
-                 reduce="none", average=True, **opt_kwargs):
+                 reduce="none", average=True, compression="none",
+                 **opt_kwargs):
         """reduce: "none" (grads already reduced, e.g. by DistributedData)
-        or "rs" (this wrapper reduce-scatters raw local grads itself)."""
+        or "rs" (this wrapper reduce-scatters raw local grads itself).
+        compression: "none", or "int8" for the quantized reduce_scatter
+        (needs reduce="rs" and f32 or bf16 parameters; block size from
+        mx.set_quant_params). A group of one exchanges nothing either way."""
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
@@ -51,6 +58,12 @@ class ShardedOptimizer:
         self.average = average
         assert reduce in ("none", "rs")
         self.reduce = reduce
+        if compression not in ("none", "int8"):
+            raise ValueError(f"compression={compression!r}: expected 'none' or 'int8'")
+        if compression == "int8" and reduce != "rs":
+            raise ValueError('compression="int8" compresses the gradient '
+                             'reduce_scatter: it needs reduce="rs"')
+        self.compression = compression
 
         if torch.cuda.is_available() and self.params[0].is_cuda:
             mx.set_compute_stream(torch.cuda.current_stream().cuda_stream)
@@ -58,6 +71,8 @@ class ShardedOptimizer:
         dt = self.params[0].dtype
         assert all(p.dtype == dt for p in self.params), \
             "one flat group: uniform dtype required"
+        if compression == "int8" and dt not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'compression="int8" supports f32/bf16 parameters, not {dt}')
         total = sum(p.numel() for p in self.params)
         # pad so the shard divides evenly (owned = ceil math in the
         # reference, mlsl_impl.cpp:401-411; padding is the flat analog)
@@ -79,6 +94,12 @@ class ShardedOptimizer:
         shard_param = torch.nn.Parameter(self.own_param, requires_grad=False)
         self._shard_holder = shard_param
         self.opt = opt_cls([shard_param], **opt_kwargs)
+        # built once: the request owns the error-feedback residual
+        self._qrs = None
+        if compression == "int8" and self.world > 1:
+            self._qrs = mx.PersistentRequest(self.dist, "reduce_scatter", self.shard,
+                                             dtype=_dt(self.flat), op="sum",
+                                             group=group, quantized=True)
 
     def _gather_grads(self):
         off = 0
@@ -95,7 +116,12 @@ class ShardedOptimizer:
     def step(self):
         self._gather_grads()
         if self.world > 1:
-            if self.reduce == "rs":
+            if self._qrs is not None:
+                # in place: every segment is on the wire before the owned
+                # shard is written
+                self._qrs.start(self.flat_grad, self.own_grad)
+                self._qrs.wait()
+            elif self.reduce == "rs":
                 # raw local grads -> reduce_scatter into the owned shard
                 mx.wait(self.dist.reduce_scatter(
                     self.flat_grad, self.own_grad, self.shard, op="sum",
