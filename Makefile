@@ -118,11 +118,25 @@ $(ASAN): mlsl_amd/csrc/tests/schedule_selftest.cpp mlsl_amd/csrc/comm/schedule.c
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -o $@
 
+# One-shot quantized reduce-scatter under ASan/UBSan: its schedule (matching,
+# slot layout, routing) and the host codec walked through the exchange by
+# hand. Pure host C++, like the target above.
+ASAN_QRS_DIRECT := $(BUILD)/quant_rs_direct_selftest_asan
+
+asan-quant-rs-direct: $(ASAN_QRS_DIRECT)
+	$(ASAN_QRS_DIRECT)
+
+$(ASAN_QRS_DIRECT): mlsl_amd/csrc/tests/quant_rs_direct_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/core/log.cpp
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $^ -pthread -ldl -o $@
+
 # Full-stack ASan: the API selftest (planner+engine+mesh, TCP world
 # matrix) host-compiled with g++ + ASan/UBSan; device kernels stubbed.
 ASAN_API := $(BUILD)/api_selftest_asan
 ASAN_SRC := $(CSRC) mlsl_amd/csrc/tests/api_selftest.cpp             mlsl_amd/csrc/tests/asan_kernel_stubs.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp
+    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp \
+    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs_direct.cpp
 
 asan-api: $(ASAN_API)
 
@@ -144,7 +158,8 @@ $(TSAN_API): $(ASAN_SRC)
 TSAN_SUBMIT := $(BUILD)/submit_race_tsan
 TSAN_SUBMIT_SRC := $(CSRC) mlsl_amd/csrc/tests/submit_race_selftest.cpp \
     mlsl_amd/csrc/tests/asan_kernel_stubs.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp
+    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp \
+    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs_direct.cpp
 
 tsan-submit: $(TSAN_SUBMIT)
 

@@ -7,8 +7,13 @@ Launch with torchrun for N>1.
 hop — the fused quant_sum_dequant kernel against the sequence it replaces,
 quant_accum followed by dequantize of the same wires (--melems elements,
 block 256, f32 and bf16; interleaved rounds in one process).
---mode reduce_scatter: quantized against exact reduce-scatter of --melems
-elements per rank (launch with benchmarks/mp_run.py for N>1)."""
+--mode sum_dequant_n_ab: single-GPU A/B of the one-shot reduce-scatter's
+fan-in at N = 4 and 8 wires: the fused quant_sum_dequant_n kernel against the
+chain of kernels the ring runs on one segment, N-2 quant_accum plus one
+quant_sum_dequant (--melems elements, block 256, f32 and bf16).
+--mode reduce_scatter: quantized (ring, and direct up to 8 ranks) against
+exact reduce-scatter of --melems elements per rank (launch with
+benchmarks/mp_run.py for N>1)."""
 import argparse
 import json
 import os
@@ -94,12 +99,83 @@ def sum_dequant_ab(args):
         del out
 
 
+def sum_dequant_n_ab(args):
+    """One line of JSON per (N, dtype). Timing as in sum_dequant_ab: host
+    clock around `iters` launch+sync pairs, interleaved rounds. The chain is
+    what the ring spends on one segment across its N-1 hops (on N-1 different
+    ranks, one after the other); its accumulator is not reset between calls,
+    which changes values and not the bytes moved."""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("sum_dequant_n_ab measures GPU kernels: no GPU found")
+    from mlsl_amd import ops
+    torch.cuda.set_device(0)
+    count, block = args.melems << 20, 256
+    wbytes = ops.wire_bytes(count, block)
+    torch.manual_seed(0)
+    wires = []
+    for k in range(8):
+        v = torch.randn(count, dtype=torch.float32, device="cuda") * (1.0 + k)
+        wire = torch.empty(wbytes, dtype=torch.uint8, device="cuda")
+        ops.quantize(v, wire, count, block=block, dtype="f32")
+        wires.append(wire)
+        del v
+    acc = wires[0].clone()
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters
+
+    for n in (4, 8):
+        for dtype, tdt, es in (("f32", torch.float32, 4), ("bf16", torch.bfloat16, 2)):
+            out = torch.empty(count, dtype=tdt, device="cuda")
+
+            def chain():
+                for k in range(1, n - 1):
+                    ops.quant_accum(acc, wires[k], count, block=block)
+                ops.quant_sum_dequant(acc, wires[n - 1], out, count, block=block,
+                                      dtype=dtype)
+
+            variants = {
+                "chain": chain,
+                "fused_n": lambda: ops.quant_sum_dequant_n(wires[:n], out, count,
+                                                           block=block, dtype=dtype),
+                "call_overhead": lambda: ops.quant_sum_dequant_n(wires[:n], out, block,
+                                                                 block=block, dtype=dtype),
+            }
+            for fn in variants.values():
+                for _ in range(args.warmup):
+                    fn()
+            times = {k: [] for k in variants}
+            for _ in range(args.rounds):
+                for k, fn in variants.items():
+                    times[k].append(timed(fn))
+            res = {"config": "quant-sum-dequant-n-ab", "nwires": n, "dtype": dtype,
+                   "melems": args.melems, "block": block, "iters": args.iters,
+                   "rounds": args.rounds}
+            for k, v in times.items():
+                res[f"{k}_us_median"] = round(_median(v) * 1e6, 1)
+                res[f"{k}_us_min"] = round(min(v) * 1e6, 1)
+            # bytes the fused kernel has to move: n wires in, one element out
+            fused_bytes = n * wbytes + count * es
+            res["fused_n_TBps"] = round(fused_bytes / _median(times["fused_n"]) / 1e12, 3)
+            res["fused_n_over_chain"] = round(_median(times["fused_n"]) /
+                                              _median(times["chain"]), 3)
+            print(json.dumps(res), flush=True)
+            del out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="allreduce",
-                    choices=["allreduce", "reduce_scatter", "sum_dequant_ab"])
+                    choices=["allreduce", "reduce_scatter", "sum_dequant_ab",
+                             "sum_dequant_n_ab"])
     ap.add_argument("--melems", type=int, default=64,
-                    help="Mi elements (per rank) for the two reduce-scatter modes")
+                    help="Mi elements (per rank) for the reduce-scatter and kernel A/B modes")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mbytes", type=int, default=256)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
@@ -109,6 +185,8 @@ def main():
     args = ap.parse_args()
     if args.mode == "sum_dequant_ab":
         return sum_dequant_ab(args)
+    if args.mode == "sum_dequant_n_ab":
+        return sum_dequant_n_ab(args)
     rs = args.mode == "reduce_scatter"
 
     use_cuda = False
@@ -157,6 +235,11 @@ def main():
                                 op="sum", group="data", quantized=True)
     xreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype,
                                 op="sum", group="data")
+    # the one-shot quantized reduce-scatter next to the ring (the default)
+    dreq = None
+    if rs and size <= 8:
+        dreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype, op="sum",
+                                    group="data", quantized=True, algo="direct")
     if rs:
         out_q, out_x = out_q[:req_count], out_x[:req_count]
 
@@ -169,7 +252,11 @@ def main():
         req.wait()
 
     results = {}
-    for name, req, out in (("quantized", qreq, out_q), ("exact", xreq, out_x)):
+    todo = [("quantized", qreq, out_q), ("exact", xreq, out_x)]
+    if dreq is not None:
+        out_d = out_q.clone() if use_cuda else out_q.copy()
+        todo.insert(1, ("quantized_direct", dreq, out_d))
+    for name, req, out in todo:
         for _ in range(args.warmup):
             run(req, out)
         sync()
@@ -205,6 +292,8 @@ def main():
         }))
     qreq.destroy()
     xreq.destroy()
+    if dreq is not None:
+        dreq.destroy()
     mx.finalize()
 
 

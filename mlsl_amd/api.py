@@ -13,6 +13,7 @@ DTYPE = {"f32": 0, "f64": 1, "u8": 2, "bf16": 3, "f16": 4, "i32": 5, "i64": 6}
 DTYPE_SIZE = {"f32": 4, "f64": 8, "u8": 1, "bf16": 2, "f16": 2, "i32": 4, "i64": 8}
 REDOP = {"sum": 0, "min": 1, "max": 2}
 GROUP = {"data": 0, "model": 1, "global": 2}
+QUANT_RS_ALGO = {"ring": 0, "direct": 1}
 OPTYPE = {"cc": 0, "bias": 1, "act": 2, "pool": 3, "split": 4, "concat": 5,
           "bcast": 6, "reduce": 7, "data": 8, "eval": 9}
 COMPRESSION = {"none": 0, "int8": 1}
@@ -383,8 +384,18 @@ class PersistentRequest:
     at construction, start/wait/test are allocation-free."""
 
     def __init__(self, dist, kind, count, dtype="f32", op="sum", group="global",
-                 quantized=False):
+                 quantized=False, algo=None):
+        """algo: quantized reduce_scatter only. None takes MLSL_QUANT_RS_ALGO
+        (ring unless set); "ring" or "direct" names it. See
+        mlsl_persistent_reduce_scatter_quantized_algo."""
         import ctypes as _c
+        if algo is not None:
+            if kind != "reduce_scatter" or not quantized:
+                raise ValueError('algo= selects the quantized reduce_scatter\'s '
+                                 'algorithm: it needs kind="reduce_scatter" and '
+                                 'quantized=True')
+            if algo not in QUANT_RS_ALGO:
+                raise ValueError(f"algo={algo!r}: expected None, 'ring' or 'direct'")
         L = lib()
         if not hasattr(L, "_persist_declared"):
             P = _c.POINTER
@@ -394,6 +405,8 @@ class PersistentRequest:
                                                          c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_reduce_scatter_quantized.argtypes = [
                 c_void_p, c_size_t, c_int, c_int, c_int, P(c_void_p)]
+            L.mlsl_persistent_reduce_scatter_quantized_algo.argtypes = [
+                c_void_p, c_size_t, c_int, c_int, c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_all_gather.argtypes = [c_void_p, c_size_t, c_int, c_int,
                                                      P(c_void_p)]
             L.mlsl_persistent_all_to_all.argtypes = [c_void_p, c_size_t, c_int, c_int,
@@ -404,6 +417,7 @@ class PersistentRequest:
             L.mlsl_request_destroy.argtypes = [c_void_p]
             for n in ("mlsl_persistent_all_reduce", "mlsl_persistent_reduce_scatter",
                       "mlsl_persistent_reduce_scatter_quantized",
+                      "mlsl_persistent_reduce_scatter_quantized_algo",
                       "mlsl_persistent_all_gather", "mlsl_persistent_all_to_all",
                       "mlsl_request_start", "mlsl_request_wait", "mlsl_request_test",
                       "mlsl_request_destroy"):
@@ -417,10 +431,19 @@ class PersistentRequest:
         elif kind == "reduce_scatter":
             # int8 wire with error feedback; raises for anything but a sum
             # of f32/bf16 rather than running the exact collective instead
-            fn = (L.mlsl_persistent_reduce_scatter_quantized if quantized
-                  else L.mlsl_persistent_reduce_scatter)
-            check(fn(dist._h, count, DTYPE[dtype], REDOP[op], GROUP[group],
-                     ctypes.byref(h)))
+            if algo is not None:
+                # "ring" requantizes on every hop but the last; "direct" sends
+                # each segment to its owner and sums N wires once (at most 8
+                # ranks, no compression plugin, N-1 segment-wires of scratch)
+                check(L.mlsl_persistent_reduce_scatter_quantized_algo(
+                    dist._h, count, DTYPE[dtype], REDOP[op], GROUP[group],
+                    QUANT_RS_ALGO[algo], ctypes.byref(h)))
+            else:
+                # algo=None: MLSL_QUANT_RS_ALGO decides (ring unless set)
+                fn = (L.mlsl_persistent_reduce_scatter_quantized if quantized
+                      else L.mlsl_persistent_reduce_scatter)
+                check(fn(dist._h, count, DTYPE[dtype], REDOP[op], GROUP[group],
+                         ctypes.byref(h)))
         elif kind == "all_gather":
             check(L.mlsl_persistent_all_gather(dist._h, count, DTYPE[dtype],
                                                GROUP[group], ctypes.byref(h)))

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "../comm/group.hpp"
+#include "../core/config.hpp"
 #include "../core/log.hpp"
 #include "../dl/rma.hpp"
 #include "../dl/session.hpp"
@@ -257,10 +258,11 @@ int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
     C_CATCH
 }
 
-int mlsl_persistent_reduce_scatter_quantized(mlsl_distribution d, size_t recv_count,
-                                             mlsl_data_type dt, mlsl_reduction op,
-                                             mlsl_group g, mlsl_request* out) {
-    C_TRY
+namespace {
+
+CommRequest* NewQuantizedReduceScatter(mlsl_distribution d, size_t recv_count,
+                                       mlsl_data_type dt, mlsl_reduction op,
+                                       mlsl_group g, QuantRsAlgo algo) {
     // never fall back to an exact reduce-scatter behind the caller's back
     MLSL_CHECK(ROP(op) == ReduceOp::SUM,
                "quantized reduce_scatter supports the SUM reduction only");
@@ -270,8 +272,33 @@ int mlsl_persistent_reduce_scatter_quantized(mlsl_distribution d, size_t recv_co
     r->AddReduceScatter(recv_count, ROP(op));
     r->SetCompression(Compression::QUANT_INT8,
                       Environment::GetEnv().GetQuantizationParams());
+    r->SetQuantRsAlgo(algo);
     r->Setup();
-    *out = r.release();
+    return r.release();
+}
+
+}  // namespace
+
+int mlsl_persistent_reduce_scatter_quantized(mlsl_distribution d, size_t recv_count,
+                                             mlsl_data_type dt, mlsl_reduction op,
+                                             mlsl_group g, mlsl_request* out) {
+    C_TRY
+    // the request names no algorithm: MLSL_QUANT_RS_ALGO decides (ring unless set)
+    *out = NewQuantizedReduceScatter(d, recv_count, dt, op, g,
+                                     GlobalConfig().quant_rs_algo);
+    C_CATCH
+}
+
+int mlsl_persistent_reduce_scatter_quantized_algo(mlsl_distribution d, size_t recv_count,
+                                                  mlsl_data_type dt, mlsl_reduction op,
+                                                  mlsl_group g, mlsl_quant_rs_algo algo,
+                                                  mlsl_request* out) {
+    C_TRY
+    MLSL_CHECK(algo == MLSL_QRS_RING || algo == MLSL_QRS_DIRECT,
+               "unknown quantized reduce_scatter algorithm");
+    *out = NewQuantizedReduceScatter(
+        d, recv_count, dt, op, g,
+        algo == MLSL_QRS_DIRECT ? QuantRsAlgo::DIRECT : QuantRsAlgo::RING);
     C_CATCH
 }
 

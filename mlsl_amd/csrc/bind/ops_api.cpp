@@ -130,6 +130,14 @@ int mlsl_hip_quant_sum_dequant_nt(const void* a_wire, const void* b_wire, void* 
     OPS_CATCH
 }
 
+int mlsl_hip_quant_sum_dequant_n(const void* const* wires, int nwires, void* out,
+                                 size_t count, size_t block, int dt) {
+    OPS_TRY LaunchQuantSumDequantN(wires, nwires, out, count, block,
+                                   static_cast<DataType>(dt), nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
 // Host codec (comm/quant.cpp) on host pointers: same wire format and the
 // same argument order as the device ops above.
 int mlsl_host_quantize(const void* in, void* err, void* wire, size_t count,
@@ -155,6 +163,13 @@ int mlsl_host_quant_sum_dequant(const void* a_wire, const void* b_wire, void* ou
                                 size_t count, size_t block, int dt) {
     OPS_TRY HostQuantSumDequant(a_wire, b_wire, out, count, block,
                                 static_cast<DataType>(dt));
+    OPS_CATCH
+}
+
+int mlsl_host_quant_sum_dequant_n(const void* const* wires, int nwires, void* out,
+                                  size_t count, size_t block, int dt) {
+    OPS_TRY HostQuantSumDequantN(wires, nwires, out, count, block,
+                                 static_cast<DataType>(dt));
     OPS_CATCH
 }
 

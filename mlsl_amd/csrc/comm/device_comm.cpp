@@ -373,12 +373,27 @@ void QuantPrologue(CommRequest* req, const ChunkExec& ce, const QuantScratch& q,
 // Allreduce (and any op on a group of one): dequantize the result wire.
 // Reduce-scatter: the partial sum that arrived last sits in its TMP slot;
 // one fused kernel adds this rank's own wire segment and writes elements.
+// One-shot reduce-scatter (fan_in > 0): N-1 wires arrived, and one N-way
+// kernel sums them with the own segment.
 void QuantEpilogue(CommRequest* req, const ChunkExec& ce, const QuantScratch& q,
                    uint8_t* rbuf, hipStream_t s) {
     const OpSpec& spec = req->Spec();
     const size_t blk = req->QParams().block_elems;
     const BufRef& res = ce.sch.result;
-    if (res.space == Space::TMP) {
+    if (ce.sch.fan_in > 0) {
+        // one-shot exchange: every peer's wire of this rank's segment sits in
+        // that peer's TMP slot; sum them and the own segment in ascending
+        // group-rank order, once
+        const size_t n = static_cast<size_t>(req->Group()->Size());
+        const size_t me = static_cast<size_t>(req->Group()->MyIdx());
+        const size_t seg_wire = req->WireBytesFor(ce) / n;
+        const void* wires[kQuantRsDirectMaxRanks];
+        for (size_t r = 0; r < n; ++r)
+            wires[r] = r == me ? q.wire + me * seg_wire
+                               : q.scratch + res.off + (r < me ? r : r - 1) * seg_wire;
+        LaunchQuantSumDequantN(wires, static_cast<int>(n), rbuf, spec.count, blk,
+                               req->Dtype(), s);
+    } else if (res.space == Space::TMP) {
         const size_t n = static_cast<size_t>(req->Group()->Size());
         const uint8_t* own = q.wire + static_cast<size_t>(req->Group()->MyIdx()) *
                                           (req->WireBytesFor(ce) / n);

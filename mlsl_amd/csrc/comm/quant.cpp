@@ -155,6 +155,36 @@ void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
     }
 }
 
+void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
+                          size_t block, DataType dt) {
+    CheckQuantBlock(block, "HostQuantSumDequantN");
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW("quantized sum-dequantize supports f32/bf16 only");
+    MLSL_CHECK(nwires >= 1 && nwires <= 8, "quantized sum-dequantize takes 1 to 8 wires");
+    for (int r = 0; r < nwires; ++r)
+        MLSL_CHECK(wires[r] != nullptr, "quantized sum-dequantize: null wire");
+    const size_t nblocks = (count + block - 1) / block;
+    for (size_t blk = 0; blk < nblocks; ++blk) {
+        const size_t base = blk * block;
+        const size_t n = std::min(block, count - base);
+        float s[8];
+        const int8_t* p[8];
+        for (int r = 0; r < nwires; ++r) {
+            const uint8_t* wb = static_cast<const uint8_t*>(wires[r]) + blk * (block + 8);
+            std::memcpy(&s[r], wb, 4);
+            p[r] = reinterpret_cast<const int8_t*>(wb + 8);
+        }
+        for (size_t i = 0; i < n; ++i) {
+            // wire order, one explicit fma per wire: the device kernel's bits
+            float acc = 0.f;
+            for (int r = 0; r < nwires; ++r)
+                acc = std::fmaf(static_cast<float>(p[r][i]), s[r], acc);
+            if (dt == DataType::F32) static_cast<float*>(out)[base + i] = acc;
+            else static_cast<uint16_t*>(out)[base + i] = F32B(acc);
+        }
+    }
+}
+
 const QuantPluginApi* LoadQuantPlugin(const QuantParams& qp) {
     if (qp.lib_path.empty()) return nullptr;
     static std::mutex mu;

@@ -29,6 +29,12 @@ void HostQuantAccum(void* acc_wire, const void* wire, size_t count, size_t block
 // untouched: the quantized reduce-scatter's last hop (no requantization).
 void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
                          size_t count, size_t block, DataType dt);
+// out = sum over r of dequant(wires[r]), 1 to 8 wires, none written: the
+// fan-in of the one-shot quantized reduce-scatter. Per element acc = +0, then
+// acc = fmaf(q_r, scale_r, acc) in wire order, bit for bit what
+// LaunchQuantSumDequantN computes.
+void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
+                          size_t block, DataType dt);
 
 // dlopen'd compression plugin (reference quant/quant.c ABI — Intel
 // DL-comp style). Loaded once per lib_path; used by the HOST compressed

@@ -143,6 +143,11 @@ void CommRequest::SetCompression(Compression c, const QuantParams& qp) {
     plugin_ = LoadQuantPlugin(qparams_);
 }
 
+void CommRequest::SetQuantRsAlgo(QuantRsAlgo a) {
+    MLSL_CHECK(!setup_done_, "SetQuantRsAlgo after Setup");
+    qrs_algo_ = a;
+}
+
 bool CommRequest::Compressed() const {
     return comp_ == Compression::QUANT_INT8 &&
            (spec_.op == CollOp::ALLREDUCE || spec_.op == CollOp::REDUCE_SCATTER) &&
@@ -315,9 +320,26 @@ void CommRequest::BuildChunks() {
                     // own run of wire blocks, the ring accumulates in the
                     // compressed domain, and the last hop is the fused
                     // sum-dequantize epilogue. Single chunk.
+                    // With DIRECT every segment goes straight to its owner
+                    // instead and the epilogue sums N wires: nothing is
+                    // requantized.
                     const size_t blk = qparams_.block_elems;
-                    ce.sch = BuildReduceScatterUnits(gr, gs, (spec_.count + blk - 1) / blk,
-                                                     qparams_.WireBlockBytes(), blk);
+                    const size_t units = (spec_.count + blk - 1) / blk;
+                    if (qrs_algo_ == QuantRsAlgo::DIRECT) {
+                        MLSL_CHECK(gs <= kQuantRsDirectMaxRanks,
+                                   "direct quantized reduce_scatter supports at most 8 "
+                                   "ranks per group (its fan-in takes 8 wires); use "
+                                   "the ring");
+                        MLSL_CHECK(plugin_ == nullptr,
+                                   "direct quantized reduce_scatter cannot run with a "
+                                   "compression plugin (the plugin ABI has no N-way "
+                                   "sum); use the ring or unset lib_path");
+                        ce.sch = BuildReduceScatterDirectUnits(
+                            gr, gs, units, qparams_.WireBlockBytes(), blk);
+                    } else {
+                        ce.sch = BuildReduceScatterUnits(gr, gs, units,
+                                                         qparams_.WireBlockBytes(), blk);
+                    }
                 } else if (n_chunks > 1) {
                     ce.elem_off = 0;  // chunk offsets are absolute
                     ce.sch = BuildReduceScatterChunk(
@@ -660,11 +682,21 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                     // that arrived last and this rank's own wire segment
                     // still have to meet. The plugin ABI has no fused hook,
                     // so there the sum is requantized into the arrival slot.
+                    // The one-shot schedule leaves fan_in wires in TMP, one
+                    // per peer in ascending rank order; they and the own
+                    // segment are summed in that order, once.
                     uint8_t* res = ptr(ce.sch.result);
                     const uint8_t* own =
                         nseg > 1 ? wire + static_cast<size_t>(group_->MyIdx()) * seg_wire
                                  : nullptr;
-                    if (plugin_) {
+                    if (ce.sch.fan_in > 0) {
+                        const void* wires[kQuantRsDirectMaxRanks];
+                        const size_t me = static_cast<size_t>(group_->MyIdx());
+                        for (size_t r = 0; r < nseg; ++r)
+                            wires[r] = r == me ? own : res + (r < me ? r : r - 1) * seg_wire;
+                        HostQuantSumDequantN(wires, static_cast<int>(nseg), rbase,
+                                             spec_.count, qparams_.block_elems, dtype_);
+                    } else if (plugin_) {
                         int rc = own ? plugin_->reduce_sum(
                                            own, res, seg_wire / qparams_.WireBlockBytes())
                                      : 0;

@@ -109,6 +109,12 @@ class CommRequest {
     // before Setup(); honored for ALLREDUCE and REDUCE_SCATTER with SUM on
     // f32/bf16.
     void SetCompression(Compression c, const QuantParams& qp);
+    // Algorithm of a quantized REDUCE_SCATTER (ignored by every other op).
+    // Call before Setup(). DIRECT keeps N-1 segment-wires of scratch where
+    // RING keeps 2, and Setup() fails for it on a group of more than
+    // kQuantRsDirectMaxRanks ranks or with a compression plugin.
+    void SetQuantRsAlgo(QuantRsAlgo a);
+    QuantRsAlgo GetQuantRsAlgo() const { return qrs_algo_; }
     Compression GetCompression() const { return comp_; }
     const QuantParams& QParams() const { return qparams_; }
     const struct QuantPluginApi* Plugin() const { return plugin_; }
@@ -178,6 +184,7 @@ class CommRequest {
     Compression comp_ = Compression::NONE;
     QuantParams qparams_;
     const struct QuantPluginApi* plugin_ = nullptr;  // dlopen'd compression
+    QuantRsAlgo qrs_algo_ = QuantRsAlgo::RING;
 
     std::vector<ChunkExec> chunks_;
     size_t total_tmp_bytes_ = 0;

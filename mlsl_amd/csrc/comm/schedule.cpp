@@ -339,6 +339,38 @@ Schedule BuildReduceScatterUnits(int rank, int size, size_t units_per_rank,
     return sch;
 }
 
+Schedule BuildReduceScatterDirectUnits(int rank, int size, size_t units_per_rank,
+                                       size_t unit_bytes, size_t quant_block) {
+    const size_t segB = units_per_rank * unit_bytes;
+    Schedule sch;
+    sch.dtype = DataType::U8;
+    sch.rop = ReduceOp::SUM;
+    sch.quant_block = quant_block;
+    sch.wire_bytes = static_cast<size_t>(size) * segB;
+    if (size == 1) {
+        sch.result = Ref(Space::SEND, 0, segB);
+        return sch;
+    }
+    const int N = size, r = rank;
+    sch.tmp_bytes = static_cast<size_t>(N - 1) * segB;
+    sch.fan_in = static_cast<size_t>(N - 1);
+    // BuildAlltoAllvChunk's pairwise order: exchange j pairs this rank with
+    // (rank+j)%N and (rank-j)%N. Exchange j is phase j-1; no phase is empty.
+    for (int j = 1; j < N; ++j) {
+        const int to = (r + j) % N, from = (r - j + N) % N;
+        Step st;
+        st.phase = j - 1;
+        st.send_peer = to;
+        st.send = Ref(Space::SEND, static_cast<size_t>(to) * segB, segB);
+        st.recv_peer = from;
+        st.recv = Ref(Space::TMP, static_cast<size_t>(from < r ? from : from - 1) * segB,
+                      segB);
+        sch.AddStep(st);
+    }
+    sch.result = Ref(Space::TMP, 0, sch.tmp_bytes);
+    return sch;
+}
+
 // Chunked reduce-scatter: the chunk covers output elements [off, off+cnt)
 // of every rank's recv_count-long segment; SEND reads use the FULL-buffer
 // row stride (total*es per rank-row) so independent chunks cover the whole

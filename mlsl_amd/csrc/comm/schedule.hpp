@@ -64,6 +64,11 @@ struct Schedule {
     // SEND/RECV refs address. Equals result.bytes for the allreduce; the
     // reduce-scatter's wire holds N segments and its result only one.
     size_t wire_bytes = 0;
+    // >0 (one-shot quantized reduce-scatter only): this many wires arrived,
+    // one per equal TMP slot in ascending peer-rank order; the result is
+    // their sum with this rank's own SEND segment, taken by the executor's
+    // N-way sum-dequantize epilogue. 0 everywhere else.
+    size_t fan_in = 0;
     // Direct (one-shot) allreduce shape: phase 1 is "send TMP(0,B) to all
     // peers, receive each peer's TMP slot, reduce all into RECV(0,B)" —
     // executors may batch it into fan-out/fan-in kernels.
@@ -105,6 +110,18 @@ Schedule BuildAllReduceRingUnits(int rank, int size, size_t units, size_t unit_b
 // executor's fused sum-dequantize epilogue. size == 1 has no traffic.
 Schedule BuildReduceScatterUnits(int rank, int size, size_t units_per_rank,
                                  size_t unit_bytes, size_t quant_block);
+// One-shot (direct) reduce-scatter over the same wire units: N-1 pairwise
+// exchanges in BuildAlltoAllvChunk's (rank±j)%N order. Exchange j sends wire
+// segment `to` straight to its owner to = (rank+j)%N and receives this
+// rank's segment from from = (rank-j+N)%N into that peer's own TMP slot
+// (slot index from < rank ? from : from-1, i.e. ascending rank order with
+// this rank left out). No step has a local op and nothing is requantized:
+// fan_in = N-1 tells the executor that the result is the N-way sum of the
+// TMP slots and this rank's own SEND segment, and `result` names the whole
+// TMP range. Sends the ring's wire bytes per rank, (N-1)/N of the wire, but
+// needs N-1 segment-wires of scratch where the ring needs 2.
+Schedule BuildReduceScatterDirectUnits(int rank, int size, size_t units_per_rank,
+                                       size_t unit_bytes, size_t quant_block);
 Schedule BuildAllReduceRHD(int rank, int size, size_t count, DataType dt, ReduceOp op);
 // One-shot exchange + local reduce (latency-optimal on full-mesh xGMI;
 // (N-1)x wire cost — small messages only).

@@ -47,6 +47,11 @@ Config Config::FromEnv() {
     c.msg_priority = EnvBool("MLSL_MSG_PRIORITY", false);
     c.msg_priority_threshold = EnvSize("MLSL_MSG_PRIORITY_THRESHOLD", 10000);
     c.quant_block = EnvSize("MLSL_QUANT_BLOCK", 256);
+    if (const char* e = std::getenv("MLSL_QUANT_RS_ALGO")) {
+        if (!std::strcmp(e, "direct")) c.quant_rs_algo = QuantRsAlgo::DIRECT;
+        else if (!std::strcmp(e, "ring") || !*e) c.quant_rs_algo = QuantRsAlgo::RING;
+        else MLSL_THROW(std::string("MLSL_QUANT_RS_ALGO=") + e + ": expected ring or direct");
+    }
     c.heap_mb = EnvSize("MLSL_HEAP_SIZE_MB", 0);
     c.check_pointers = EnvBool("MLSL_CHECK_POINTERS", false);
     if (const char* e = std::getenv("MLSL_TRANSPORT")) c.transport = e;

@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <string>
 
+#include "types.hpp"
+
 namespace mlsl {
 
 enum class ProgressMode : int {
@@ -39,6 +41,9 @@ struct Config {
     size_t msg_priority_threshold = 10000;  // MLSL_MSG_PRIORITY_THRESHOLD bytes
     bool msg_priority = false;     // MLSL_MSG_PRIORITY: newest-first scheduling
     size_t quant_block = 256;      // MLSL_QUANT_BLOCK: elems per int8 quant block
+    // MLSL_QUANT_RS_ALGO=ring|direct: quantized reduce-scatter requests that
+    // do not name an algorithm
+    QuantRsAlgo quant_rs_algo = QuantRsAlgo::RING;
     size_t heap_mb = 0;            // MLSL_HEAP_SIZE_MB: device pool pre-reserve
     bool check_pointers = false;   // MLSL_CHECK_POINTERS: validate collective bufs
     std::string transport = "auto";  // MLSL_TRANSPORT=auto|tcp|rccl

@@ -93,6 +93,16 @@ enum class Compression : int {
     QUANT_INT8 = 1,   // block int8 quantization with error feedback
 };
 
+// How a quantized reduce-scatter moves its wire (MLSL_QUANT_RS_ALGO, or per
+// request). RING requantizes the partial sum on every hop but the last;
+// DIRECT sends each segment straight to its owner and sums N wires once.
+enum class QuantRsAlgo : int {
+    RING = 0,
+    DIRECT = 1,
+};
+// DIRECT's fan-in kernel takes the wires by value: at most this many ranks.
+constexpr int kQuantRsDirectMaxRanks = 8;
+
 // Block-quantization parameters (reference QuantParams
 // include/mlsl.hpp:162-171). Built-in int8 HIP/CPU kernels by default; a
 // dlopen'd user library (Intel DL-comp-style quantize/dequantize/

@@ -760,6 +760,100 @@ __global__ void QuantSumDequantX2Kernel(const uint8_t* __restrict__ a,
     });
 }
 
+// N-way fan-in of the one-shot quantized reduce-scatter: out = the sum of NW
+// dequantized wires, each quantized once and none requantized. The wire
+// pointers travel by value in the kernarg (as FanKernArgs does), so they are
+// scalar loads and no table has to live in device memory.
+constexpr int kMaxSumWires = 8;
+struct QuantWires {
+    const uint8_t* w[kMaxSumWires];
+};
+
+// Byte j of each wire's packed word, summed in wire order from +0 with one
+// explicit fma per wire: the result is a fixed function of the wires that no
+// contraction setting can change (a*b + c*d may or may not be fused).
+template <int NW>
+__device__ __forceinline__ float QFmaSum(const int32_t (&p)[NW], const float (&s)[NW],
+                                         int j) {
+    float acc = 0.f;
+#pragma unroll
+    for (int r = 0; r < NW; ++r)
+        acc = __builtin_fmaf(static_cast<float>(QUnpack(p[r], j)), s[r], acc);
+    return acc;
+}
+
+// Generic path: any legal block, partial last block, unaligned `out`. All NW
+// loads of a pass are issued before the first fma, so they are in flight
+// together.
+template <typename T, int NW>
+__global__ void QuantSumDequantNKernel(QuantWires ws, T* __restrict__ out, size_t count,
+                                       size_t block_elems) {
+    const bool vec4 = (block_elems & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    ForEachWaveBlock((count + block_elems - 1) / block_elems, [&](size_t vblk, int lane) {
+        // The block index is the same in all 64 lanes; saying so keeps the
+        // NW block addresses in scalar registers (with 8 wires they spilled
+        // as per-lane values).
+        const size_t blk =
+            (static_cast<size_t>(__builtin_amdgcn_readfirstlane(
+                 static_cast<uint32_t>(vblk >> 32))) << 32) |
+            static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vblk)));
+        const size_t base = blk * block_elems;
+        const size_t n = min(block_elems, count - base);
+        const int8_t* payload[NW];
+        float s[NW];
+#pragma unroll
+        for (int r = 0; r < NW; ++r) {
+            const uint8_t* wblock = ws.w[r] + blk * (block_elems + kWireHdr);
+            s[r] = WireScale(wblock);
+            payload[r] = reinterpret_cast<const int8_t*>(wblock + kWireHdr);
+        }
+        ForEachBlockElem(n, vec4, lane, [&](size_t i, auto w) {
+            constexpr int W = decltype(w)::value;
+            int32_t p[NW];
+#pragma unroll
+            for (int r = 0; r < NW; ++r) p[r] = QLoad<W>(payload[r], i);
+            if constexpr (W == 4) {
+                std::conditional_t<sizeof(T) == 4, float4_ev, ushort4_t> v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = Encode<T>(QFmaSum<NW>(p, s, j));
+                StoreVec<false>(v, out + base + i);
+            } else {
+                out[base + i] = Encode<T>(QFmaSum<NW>(p, s, 0));
+            }
+        });
+    });
+}
+
+// Fast path (block_elems == 256, whole blocks, 16-B aligned `out`): one
+// block per half-wave, 8 consecutive elements per lane, so each wire costs a
+// lane one 8-B payload load (wires are only 8-B aligned) and the output one
+// 16-B store for bf16, two for f32.
+template <typename T, int NW>
+__global__ void QuantSumDequantNX2Kernel(QuantWires ws, T* __restrict__ out,
+                                         size_t nblocks) {
+    ForEachHalfWaveBlock(nblocks, [&](size_t blk, int sub) {
+        uint2_ev pw[NW];
+        float s[NW];
+#pragma unroll
+        for (int r = 0; r < NW; ++r) {
+            const uint8_t* wblock = ws.w[r] + blk * (kFastBlock + kWireHdr);
+            s[r] = WireScale(wblock);
+            pw[r] = *reinterpret_cast<const uint2_ev*>(wblock + kWireHdr + sub * 8);
+        }
+        float o[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            int32_t p[NW];
+#pragma unroll
+            for (int r = 0; r < NW; ++r) p[r] = static_cast<int32_t>(pw[r][h]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[4 * h + j] = QFmaSum<NW>(p, s, j);
+        }
+        Store8<false>(out + blk * kFastBlock + sub * 8, o);
+    });
+}
+
 inline size_t NumBlocks(size_t count, size_t block_elems) {
     return (count + block_elems - 1) / block_elems;
 }
@@ -957,6 +1051,62 @@ void LaunchQuantSumDequantNT(const void* a_wire, const void* b_wire, void* out,
     // A/B hook: the fast path with nontemporal stores of `out` at any size.
     QuantSumDequantAny(a_wire, b_wire, out, count, block_elems, dt, /*force_nt=*/true,
                        stream, "LaunchQuantSumDequantNT");
+}
+
+namespace {
+
+// f(integral_constant<int, nwires>) for nwires in [1, kMaxSumWires]
+template <typename F>
+void DispatchWires(int nwires, F&& f) {
+    switch (nwires) {
+#define MLSL_WIRES_CASE(N) case N: f(std::integral_constant<int, N>{}); break;
+        MLSL_WIRES_CASE(1) MLSL_WIRES_CASE(2) MLSL_WIRES_CASE(3) MLSL_WIRES_CASE(4)
+        MLSL_WIRES_CASE(5) MLSL_WIRES_CASE(6) MLSL_WIRES_CASE(7) MLSL_WIRES_CASE(8)
+#undef MLSL_WIRES_CASE
+        default: MLSL_THROW("quantized sum-dequantize: wire count out of range");
+    }
+}
+
+template <typename T>
+void QuantSumDequantNTyped(const QuantWires& ws, int nwires, bool x2, void* out,
+                           size_t count, size_t block_elems, hipStream_t stream) {
+    const size_t nblocks = NumBlocks(count, block_elems);
+    DispatchWires(nwires, [&](auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        if (x2)
+            QuantSumDequantNX2Kernel<T, NW><<<PairGrid(nblocks), dim3(kBlock), 0, stream>>>(
+                ws, static_cast<T*>(out), nblocks);
+        else
+            QuantSumDequantNKernel<T, NW><<<WaveGrid(nblocks), dim3(kBlock), 0, stream>>>(
+                ws, static_cast<T*>(out), count, block_elems);
+    });
+}
+
+}  // namespace
+
+void LaunchQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
+                            size_t block_elems, DataType dt, hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchQuantSumDequantN");
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW("quantized sum-dequantize supports f32/bf16 only");
+    MLSL_CHECK(nwires >= 1 && nwires <= kMaxSumWires,
+               "quantized sum-dequantize takes 1 to 8 wires");
+    if (count == 0) return;
+    QuantWires ws{};
+    // same fast-path rule as SumDequantX2Eligible, over every wire
+    bool x2 = block_elems == kFastBlock && count % kFastBlock == 0 &&
+              (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    for (int r = 0; r < nwires; ++r) {
+        MLSL_CHECK(wires[r] != nullptr, "quantized sum-dequantize: null wire");
+        ws.w[r] = static_cast<const uint8_t*>(wires[r]);
+        x2 = x2 && (reinterpret_cast<uintptr_t>(wires[r]) & 7) == 0;
+    }
+    if (dt == DataType::F32)
+        QuantSumDequantNTyped<float>(ws, nwires, x2, out, count, block_elems, stream);
+    else
+        QuantSumDequantNTyped<unsigned short>(ws, nwires, x2, out, count, block_elems,
+                                              stream);
+    HIP_CHECK(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------

@@ -60,6 +60,14 @@ void LaunchQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
 void LaunchQuantSumDequantNT(const void* a_wire, const void* b_wire, void* out,
                              size_t count, size_t block_elems, DataType dt,
                              hipStream_t stream);
+// N-way fan-in of the one-shot quantized reduce-scatter: out[i] = the sum of
+// dequant(wires[r])[i] over r = 0..nwires-1 (1 to 8 wires, fp32/bf16 out).
+// Per element acc = +0, then acc = fma(q_r, scale_r, acc) in wire order,
+// rounded once into the element type; the host twin computes the same bits.
+// `wires` is a host array read during the call; no wire is written and
+// nothing past out[count) is.
+void LaunchQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
+                            size_t block_elems, DataType dt, hipStream_t stream);
 
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,

@@ -111,6 +111,21 @@ int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
 int mlsl_persistent_reduce_scatter_quantized(mlsl_distribution d, size_t recv_count,
                                              mlsl_data_type dt, mlsl_reduction op,
                                              mlsl_group g, mlsl_request* out);
+/* The same collective with its algorithm named (the function above takes
+ * MLSL_QUANT_RS_ALGO=ring|direct, default ring).
+ * MLSL_QRS_RING: N-1 hops; every hop but the last requantizes the partial
+ * sum, so the error grows with the group and the residual only holds this
+ * rank's own first quantization error. Scratch: 2 segment-wires.
+ * MLSL_QRS_DIRECT: wire segment j goes straight to rank j and each rank adds
+ * the N wires of its segment in one pass. Nothing is requantized, the
+ * residual holds all of the error, the wire bytes sent per rank are the
+ * ring's. Scratch: N-1 segment-wires. Fails at creation on a group of more
+ * than 8 ranks or with a compression plugin (lib_path). */
+typedef enum { MLSL_QRS_RING = 0, MLSL_QRS_DIRECT = 1 } mlsl_quant_rs_algo;
+int mlsl_persistent_reduce_scatter_quantized_algo(mlsl_distribution d, size_t recv_count,
+                                                  mlsl_data_type dt, mlsl_reduction op,
+                                                  mlsl_group g, mlsl_quant_rs_algo algo,
+                                                  mlsl_request* out);
 int mlsl_persistent_all_gather(mlsl_distribution d, size_t send_count, mlsl_data_type dt,
                                mlsl_group g, mlsl_request* out);
 int mlsl_persistent_all_to_all(mlsl_distribution d, size_t send_count, mlsl_data_type dt,

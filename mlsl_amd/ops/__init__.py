@@ -39,12 +39,17 @@ def _lib():
                                                  c.c_size_t, c.c_size_t, c.c_int]
         L.mlsl_hip_quant_sum_dequant_nt.argtypes = L.mlsl_hip_quant_sum_dequant.argtypes
         L.mlsl_host_quant_sum_dequant.argtypes = L.mlsl_hip_quant_sum_dequant.argtypes
+        L.mlsl_hip_quant_sum_dequant_n.argtypes = [c.POINTER(c.c_void_p), c.c_int,
+                                                   c.c_void_p, c.c_size_t, c.c_size_t,
+                                                   c.c_int]
+        L.mlsl_host_quant_sum_dequant_n.argtypes = L.mlsl_hip_quant_sum_dequant_n.argtypes
         L.mlsl_host_quantize.argtypes = L.mlsl_hip_quantize.argtypes
         L.mlsl_host_dequantize.argtypes = L.mlsl_hip_dequantize.argtypes
         L.mlsl_host_quant_accum.argtypes = L.mlsl_hip_quant_accum.argtypes
         for n in ("mlsl_host_quantize", "mlsl_host_dequantize", "mlsl_host_quant_accum",
                   "mlsl_hip_quant_sum_dequant", "mlsl_hip_quant_sum_dequant_nt",
-                  "mlsl_host_quant_sum_dequant"):
+                  "mlsl_host_quant_sum_dequant", "mlsl_hip_quant_sum_dequant_n",
+                  "mlsl_host_quant_sum_dequant_n"):
             getattr(L, n).restype = c.c_int
         ptypes = [c.c_void_p, c.c_void_p] + [c.c_size_t] * 8 + [c.c_int]
         L.mlsl_hip_pack.argtypes = ptypes
@@ -164,6 +169,18 @@ def quant_sum_dequant_nt(a_wire, b_wire, out, count, block=256, dtype=None):
     check(_lib().mlsl_hip_quant_sum_dequant_nt(ap, bp, op_, count, block, DTYPE[dt]))
 
 
+def quant_sum_dequant_n(wires, out, count, block=256, dtype=None):
+    """out = the sum of dequantize(w) over the 1 to 8 `wires`, in one pass and
+    in the element type of `out` (f32/bf16); no wire is written. Per element
+    the sum starts at +0 and takes one fma per wire, in the order given: the
+    fan-in of the one-shot quantized reduce-scatter (algo="direct")."""
+    ptrs = (ctypes.c_void_p * len(wires))(*[_as_ptr_dtype(w)[0].value for w in wires])
+    op_, d1 = _as_ptr_dtype(out)
+    dt = dtype or d1
+    check(_lib().mlsl_hip_quant_sum_dequant_n(ptrs, len(wires), op_, count, block,
+                                              DTYPE[dt]))
+
+
 _ELEM_BYTES = {"f32": 4, "bf16": 2}
 
 
@@ -216,6 +233,17 @@ def host_quant_sum_dequant(a_wire, b_wire, out, count, block=256, dtype="f32"):
     bp = _host_buf(b_wire, wire_bytes(count, block), "b_wire")
     op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
     check(_lib().mlsl_host_quant_sum_dequant(ap, bp, op_, count, block, DTYPE[dtype]))
+
+
+def host_quant_sum_dequant_n(wires, out, count, block=256, dtype="f32"):
+    """Host twin of `quant_sum_dequant_n` on numpy arrays: the same bits."""
+    _check_block(block)
+    ptrs = (ctypes.c_void_p * len(wires))(
+        *[_host_buf(w, wire_bytes(count, block), f"wires[{i}]").value
+          for i, w in enumerate(wires)])
+    op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
+    check(_lib().mlsl_host_quant_sum_dequant_n(ptrs, len(wires), op_, count, block,
+                                               DTYPE[dtype]))
 
 
 def pack(src, dst, *, mb_offset, mb_count, fm_offset, fm_count, fm_size,

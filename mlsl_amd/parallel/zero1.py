@@ -42,13 +42,17 @@ def _dt(t):
 
 class ShardedOptimizer:
     def __init__(self, params, opt_cls, dist=None, group="data",
-                 reduce="none", average=True, compression="none",
+                 reduce="none", average=True, compression="none", rs_algo=None,
                  **opt_kwargs):
         """reduce: "none" (grads already reduced, e.g. by DistributedData)
         or "rs" (this wrapper reduce-scatters raw local grads itself).
         compression: "none", or "int8" for the quantized reduce_scatter
         (needs reduce="rs" and f32 or bf16 parameters; block size from
-        mx.set_quant_params). A group of one exchanges nothing either way."""
+        mx.set_quant_params). A group of one exchanges nothing either way.
+        rs_algo: algorithm of that quantized reduce_scatter: None
+        (MLSL_QUANT_RS_ALGO, ring unless set), "ring", or "direct" (each shard
+        goes straight to its owner and is summed once, nothing requantized;
+        at most 8 ranks, N-1 shard-wires of scratch instead of 2)."""
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
@@ -64,6 +68,12 @@ class ShardedOptimizer:
             raise ValueError('compression="int8" compresses the gradient '
                              'reduce_scatter: it needs reduce="rs"')
         self.compression = compression
+        if rs_algo not in (None, "ring", "direct"):
+            raise ValueError(f"rs_algo={rs_algo!r}: expected None, 'ring' or 'direct'")
+        if rs_algo is not None and compression != "int8":
+            raise ValueError('rs_algo= selects the quantized reduce_scatter\'s '
+                             'algorithm: it needs compression="int8"')
+        self.rs_algo = rs_algo
 
         if torch.cuda.is_available() and self.params[0].is_cuda:
             mx.set_compute_stream(torch.cuda.current_stream().cuda_stream)
@@ -99,7 +109,8 @@ class ShardedOptimizer:
         if compression == "int8" and self.world > 1:
             self._qrs = mx.PersistentRequest(self.dist, "reduce_scatter", self.shard,
                                              dtype=_dt(self.flat), op="sum",
-                                             group=group, quantized=True)
+                                             group=group, quantized=True,
+                                             algo=rs_algo)
 
     def _gather_grads(self):
         off = 0
