@@ -19,6 +19,7 @@ CSRC := \
     mlsl_amd/csrc/core/signals.cpp \
     mlsl_amd/csrc/comm/schedule.cpp \
     mlsl_amd/csrc/comm/quant.cpp \
+    mlsl_amd/csrc/comm/quant_plan.cpp \
     mlsl_amd/csrc/comm/device_pool.cpp \
     mlsl_amd/csrc/comm/bootstrap.cpp \
     mlsl_amd/csrc/comm/mesh.cpp \
@@ -118,15 +119,16 @@ $(ASAN): mlsl_amd/csrc/tests/schedule_selftest.cpp mlsl_amd/csrc/comm/schedule.c
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -o $@
 
-# One-shot quantized reduce-scatter under ASan/UBSan: its schedule (matching,
-# slot layout, routing) and the host codec walked through the exchange by
-# hand. Pure host C++, like the target above.
+# Compressed collectives under ASan/UBSan: the one-shot reduce-scatter's
+# schedule (matching, slot layout, routing), the plan of every compressed
+# schedule, and the host codec walked through the exchange by hand over the
+# plan's layout. Pure host C++, like the target above.
 ASAN_QRS_DIRECT := $(BUILD)/quant_rs_direct_selftest_asan
 
 asan-quant-rs-direct: $(ASAN_QRS_DIRECT)
 	$(ASAN_QRS_DIRECT)
 
-$(ASAN_QRS_DIRECT): mlsl_amd/csrc/tests/quant_rs_direct_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/core/log.cpp
+$(ASAN_QRS_DIRECT): mlsl_amd/csrc/tests/quant_rs_direct_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/comm/quant_plan.cpp mlsl_amd/csrc/core/log.cpp
 	@mkdir -p $(dir $@)
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -ldl -o $@
@@ -134,9 +136,7 @@ $(ASAN_QRS_DIRECT): mlsl_amd/csrc/tests/quant_rs_direct_selftest.cpp mlsl_amd/cs
 # Full-stack ASan: the API selftest (planner+engine+mesh, TCP world
 # matrix) host-compiled with g++ + ASan/UBSan; device kernels stubbed.
 ASAN_API := $(BUILD)/api_selftest_asan
-ASAN_SRC := $(CSRC) mlsl_amd/csrc/tests/api_selftest.cpp             mlsl_amd/csrc/tests/asan_kernel_stubs.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs_direct.cpp
+ASAN_SRC := $(CSRC) mlsl_amd/csrc/tests/api_selftest.cpp mlsl_amd/csrc/tests/asan_kernel_stubs.cpp
 
 asan-api: $(ASAN_API)
 
@@ -157,9 +157,7 @@ $(TSAN_API): $(ASAN_SRC)
 # Concurrent-submit race test (multi-producer MPSC ring) under TSan.
 TSAN_SUBMIT := $(BUILD)/submit_race_tsan
 TSAN_SUBMIT_SRC := $(CSRC) mlsl_amd/csrc/tests/submit_race_selftest.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs.cpp \
-    mlsl_amd/csrc/tests/asan_kernel_stubs_quant_rs_direct.cpp
+    mlsl_amd/csrc/tests/asan_kernel_stubs.cpp
 
 tsan-submit: $(TSAN_SUBMIT)
 

@@ -326,86 +326,6 @@ DeviceRuntime* CreateDeviceRuntime() {
     return rt;
 }
 
-namespace {
-
-// Scratch of one compressed chunk: [wire][schedule scratch][residual].
-// Each region is 16-B aligned so the vectorized quant kernels' fast paths
-// apply (wire blocks are 264 B, so raw offsets are only 8-B aligned).
-struct QuantScratch {
-    uint8_t* wire;
-    uint8_t* scratch;
-    uint8_t* err;
-    size_t bytes;  // all three regions
-};
-
-// `base` may be null when only the size is wanted.
-QuantScratch QuantLayout(CommRequest* req, const ChunkExec& ce, uint8_t* base) {
-    auto al16 = [](size_t x) { return (x + 15) & ~size_t(15); };
-    const size_t wire_b = al16(req->WireBytesFor(ce));
-    const size_t scratch_b = al16(ce.sch.tmp_bytes);
-    QuantScratch q{};
-    q.bytes = wire_b + scratch_b +
-              al16(req->ResidualElems() * DtypeSize(req->Dtype()));
-    if (base) {
-        q.wire = base;
-        q.scratch = base + wire_b;
-        q.err = base + wire_b + scratch_b;
-    }
-    return q;
-}
-
-// Reduce-scatter quantizes each of its N send segments on a block grid of
-// its own, residual alongside; the allreduce is one segment. The whole send
-// buffer is on the wire before anything writes the recv buffer, so the two
-// may alias anywhere.
-void QuantPrologue(CommRequest* req, const ChunkExec& ce, const QuantScratch& q,
-                   const uint8_t* sbuf, hipStream_t s) {
-    const OpSpec& spec = req->Spec();
-    const size_t nseg = spec.op == CollOp::REDUCE_SCATTER
-                            ? static_cast<size_t>(req->Group()->Size()) : 1;
-    const size_t seg_b = spec.count * DtypeSize(req->Dtype());
-    const size_t seg_wire = req->WireBytesFor(ce) / nseg;
-    for (size_t j = 0; j < nseg; ++j)
-        LaunchQuantize(sbuf + j * seg_b, q.err + j * seg_b, q.wire + j * seg_wire,
-                       spec.count, req->QParams().block_elems, req->Dtype(), true, s);
-}
-
-// Allreduce (and any op on a group of one): dequantize the result wire.
-// Reduce-scatter: the partial sum that arrived last sits in its TMP slot;
-// one fused kernel adds this rank's own wire segment and writes elements.
-// One-shot reduce-scatter (fan_in > 0): N-1 wires arrived, and one N-way
-// kernel sums them with the own segment.
-void QuantEpilogue(CommRequest* req, const ChunkExec& ce, const QuantScratch& q,
-                   uint8_t* rbuf, hipStream_t s) {
-    const OpSpec& spec = req->Spec();
-    const size_t blk = req->QParams().block_elems;
-    const BufRef& res = ce.sch.result;
-    if (ce.sch.fan_in > 0) {
-        // one-shot exchange: every peer's wire of this rank's segment sits in
-        // that peer's TMP slot; sum them and the own segment in ascending
-        // group-rank order, once
-        const size_t n = static_cast<size_t>(req->Group()->Size());
-        const size_t me = static_cast<size_t>(req->Group()->MyIdx());
-        const size_t seg_wire = req->WireBytesFor(ce) / n;
-        const void* wires[kQuantRsDirectMaxRanks];
-        for (size_t r = 0; r < n; ++r)
-            wires[r] = r == me ? q.wire + me * seg_wire
-                               : q.scratch + res.off + (r < me ? r : r - 1) * seg_wire;
-        LaunchQuantSumDequantN(wires, static_cast<int>(n), rbuf, spec.count, blk,
-                               req->Dtype(), s);
-    } else if (res.space == Space::TMP) {
-        const size_t n = static_cast<size_t>(req->Group()->Size());
-        const uint8_t* own = q.wire + static_cast<size_t>(req->Group()->MyIdx()) *
-                                          (req->WireBytesFor(ce) / n);
-        LaunchQuantSumDequant(q.scratch + res.off, own, rbuf, spec.count, blk,
-                              req->Dtype(), s);
-    } else {
-        LaunchDequantize(q.wire + res.off, rbuf, spec.count, blk, req->Dtype(), s);
-    }
-}
-
-}  // namespace
-
 void DeviceSetupRequest(CommRequest* req, DeviceReqState& st) {
     // Persistent scratch only where the device executor needs it: the
     // compressed path (wire + residual), the custom schedule path (segment
@@ -421,8 +341,7 @@ void DeviceSetupRequest(CommRequest* req, DeviceReqState& st) {
                    "quantization plugin (lib_path) is supported on the host "
                    "transport only; device mode uses the built-in CDNA4 "
                    "kernels (unset lib_path)");
-        for (auto& ce : req->Chunks())
-            tmp += QuantLayout(req, ce, nullptr).bytes;
+        for (auto& ce : req->Chunks()) tmp += ce.qplan.bytes;
     } else if (req->UsesDeviceSchedule()) {
         for (auto& ce : req->Chunks()) tmp += ce.sch.tmp_bytes;
     }
@@ -660,7 +579,6 @@ void IssueFused(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
 // transport, OUR schedule supplies the algorithm and OUR kernels the math.
 void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
                    const uint8_t* sbase, uint8_t* rbase, uint8_t* tmp_dev) {
-    ProcessGroup* g = req->Group();
     const size_t es = DtypeSize(req->Dtype());
     const ncclDataType_t ndt = ncclUint8;  // byte-addressed transfers
 
@@ -698,24 +616,44 @@ void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t
                 if (d != src) LaunchCopy(d, src, st.local_src.bytes, s);
             } else if (ce.sch.quant_block > 0) {
                 const size_t blk = ce.sch.quant_block;
-                const size_t units = st.local_dst.bytes / (blk + 8);
+                const size_t units = st.local_dst.bytes / req->QParams().WireBlockBytes();
                 LaunchQuantAccum(d, src, units * blk, blk, s);
             } else {
                 LaunchReduce(d, src, st.local_dst.bytes / es, req->Dtype(), ce.sch.rop, s);
             }
         }
-        (void)g;
     }
 }
 
-}  // namespace
+// One compressed chunk whose plan regions (quant_plan.hpp) start at `base`:
+// quantize every send segment, residual alongside; let `walk(wire, scratch)`
+// run the schedule over the wire; finish into rbuf. `walk` is the only thing
+// the executors differ in: nothing at n=1, the IPC window walker, or the
+// RCCL one.
+template <class Walk>
+void IssueCompressed(CommRequest* req, const ChunkExec& ce, uint8_t* base,
+                     const uint8_t* sbuf, uint8_t* rbuf, hipStream_t s, Walk&& walk) {
+    const QuantPlan& p = ce.qplan;
+    const DataType dt = req->Dtype();
+    for (size_t j = 0; j < p.nseg; ++j)
+        LaunchQuantize(sbuf + j * p.seg_bytes, base + p.err_off + j * p.seg_bytes,
+                       base + j * p.seg_wire, p.count, p.block, dt, true, s);
+    walk(base, base + p.scratch_off);
+    const void* wires[kQuantRsDirectMaxRanks];
+    for (int k = 0; k < p.nwires; ++k) wires[k] = base + p.wire_off[k];
+    switch (p.finish) {
+        case QuantFinish::SUMN:
+            LaunchQuantSumDequantN(wires, p.nwires, rbuf, p.count, p.block, dt, s);
+            break;
+        case QuantFinish::SUM2:
+            LaunchQuantSumDequant(wires[0], wires[1], rbuf, p.count, p.block, dt, s);
+            break;
+        case QuantFinish::DEQUANT:
+            LaunchDequantize(wires[0], rbuf, p.count, p.block, dt, s);
+            break;
+    }
+}
 
-namespace {
-
-// Capture the eager issue body (already enqueued between Begin/End) is not
-// possible retroactively; instead IssueEager is factored so it can run (a)
-// directly or (b) inside a stream capture. Returns the stream carrying the
-// final dependency.
 bool GraphEligible(CommRequest* req, GroupComms& gc) {
     // Single effective stream only: every chunk must land on channel 0 and
     // no host staging (H2D/D2H of *pageable* memory is not capturable).
@@ -746,10 +684,6 @@ void EnsureEvents(DeviceReqState& st, size_t n) {
     }
 }
 
-}  // namespace
-
-namespace {
-
 // Completion check + the deferred pinned->user unstage memcpy (pageable
 // recv buffers: the D2H leg landed in the pinned bounce on-stream; the
 // final host copy runs once, here, after the events fire).
@@ -760,6 +694,277 @@ bool DeviceFinishIfDone(CommRequest* req, DeviceReqState& st) {
         st.unstage_pending = false;
     }
     return true;
+}
+
+// Record st.dep_event (created on first use) on `src`.
+void RecordDep(DeviceReqState& st, hipStream_t src) {
+    if (!st.dep_event)
+        HIP_CHECKD(hipEventCreateWithFlags(&st.dep_event, hipEventDisableTiming));
+    HIP_CHECKD(hipEventRecord(st.dep_event, src));
+}
+
+// The other channel streams order after what stream 0 carries so far.
+void FanOutStream0(GroupComms& gc, DeviceReqState& st) {
+    if (gc.streams.size() <= 1) return;
+    RecordDep(st, gc.streams[0]);
+    for (size_t i = 1; i < gc.streams.size(); ++i)
+        HIP_CHECKD(hipStreamWaitEvent(gc.streams[i], st.dep_event, 0));
+}
+
+// Grow a persistent HBM (or pinned host) buffer to at least `need` bytes.
+void GrowBuffer(HipRuntime* rt, void*& buf, size_t& have, size_t need, bool pinned) {
+    if (buf && have >= need) return;
+    if (pinned) {
+        if (buf) (void)hipHostFree(buf);
+        HIP_CHECKD(hipHostMalloc(&buf, need));
+    } else {
+        if (buf) rt->FreeDevice(buf);
+        buf = rt->AllocDevice(need);
+    }
+    have = need;
+}
+
+// Stage the result out: D2H into the pinned bounce (pageable user memory) or
+// straight into the user's registered buffer.
+void EnqueueUnstage(CommRequest* req, DeviceReqState& st, hipStream_t s) {
+    HIP_CHECKD(hipMemcpyAsync(
+        st.unstage_pending ? st.pin_recv : static_cast<void*>(req->UserRecvBuf()),
+        st.stage_recv, st.unstage_bytes, hipMemcpyDeviceToHost, s));
+}
+
+// Order after the caller's compute stream: the producer kernels
+// (e.g. torch backward on the default stream) must land before the
+// collective reads the buffers. When the compute stream is idle
+// (hipStreamQuery ~0.1 us) there is nothing to order against and
+// the record+wait pair (~4.5 us on the legacy stream) is skipped.
+void OrderAfterCompute(HipRuntime* rt, GroupComms& gc, DeviceReqState& st) {
+    hipStream_t comp = static_cast<hipStream_t>(rt->ComputeStream());
+    hipError_t q = hipStreamQuery(comp);
+    if (q != hipSuccess) {
+        (void)hipGetLastError();
+        RecordDep(st, comp);
+        for (hipStream_t cs : gc.streams)
+            HIP_CHECKD(hipStreamWaitEvent(cs, st.dep_event, 0));
+    }
+}
+
+// hipGraph replay (MLSL_USE_GRAPHS): same request + same buffers ->
+// launch the captured graph instead of re-enqueueing.
+bool ReplayGraph(CommRequest* req, GroupComms& gc, DeviceReqState& st) {
+    if (!st.graph_exec || req->SendBuf() != st.captured_sbuf ||
+        req->RecvBuf() != st.captured_rbuf)
+        return false;
+    HIP_CHECKD(hipGraphLaunch(st.graph_exec, gc.streams[0]));
+    EnsureEvents(st, 1);
+    HIP_CHECKD(hipEventRecord(st.events[0], gc.streams[0]));
+    st.issued = true;
+    return true;
+}
+
+// Host-buffer staging (ReplaceIn analog): stage host buffers through
+// persistent HBM so RCCL/kernels see device memory. Pageable memory
+// bounces through a persistent PINNED buffer in chunks — the H2D DMA of
+// chunk k overlaps the host memcpy of chunk k+1; already-pinned user
+// buffers DMA directly. (Classified fresh every Start:
+// hipPointerGetAttributes is ~0.3 us and a pointer-value cache would
+// misclassify a freed-and-reallocated pointer.) Returns whether either
+// buffer was staged.
+bool StageIn(CommRequest* req, HipRuntime* rt, GroupComms& gc, DeviceReqState& st,
+               hipStream_t base_s) {
+    size_t send_b = 0, recv_b = 0;
+    IoBytes(req, &send_b, &recv_b);
+    const BufClass s_cls = send_b > 0 ? ClassifyPtr(req->UserSendBuf())
+                                      : BufClass::DEV;
+    const BufClass r_cls = recv_b > 0 ? ClassifyPtr(req->UserRecvBuf())
+                                      : BufClass::DEV;
+    const bool s_host = s_cls != BufClass::DEV;
+    const bool r_host = r_cls != BufClass::DEV;
+    st.recv_staged = r_host;
+    st.unstage_pending = false;
+    constexpr size_t kStageChunk = 32u << 20;
+    if (s_host) {
+        GrowBuffer(rt, st.stage_send, st.stage_send_bytes, send_b, false);
+        if (s_cls == BufClass::PINNED) {
+            HIP_CHECKD(hipMemcpyAsync(st.stage_send, req->UserSendBuf(), send_b,
+                                      hipMemcpyHostToDevice, base_s));
+        } else {
+            GrowBuffer(rt, st.pin_send, st.pin_send_bytes, send_b, true);
+            for (size_t off = 0; off < send_b; off += kStageChunk) {
+                const size_t n = std::min(kStageChunk, send_b - off);
+                HostStageCopy(static_cast<uint8_t*>(st.pin_send) + off,
+                              req->UserSendBuf() + off, n);
+                HIP_CHECKD(hipMemcpyAsync(
+                    static_cast<uint8_t*>(st.stage_send) + off,
+                    static_cast<uint8_t*>(st.pin_send) + off, n,
+                    hipMemcpyHostToDevice, base_s));
+            }
+        }
+        FanOutStream0(gc, st);
+    }
+    if (r_host) {
+        GrowBuffer(rt, st.stage_recv, st.stage_recv_bytes, recv_b, false);
+        if (r_cls == BufClass::PAGEABLE)
+            GrowBuffer(rt, st.pin_recv, st.pin_recv_bytes, recv_b, true);
+        // Pageable: D2H lands in the pinned bounce; the final pinned->user
+        // memcpy runs host-side once the completion events fire.
+        st.unstage_pending = r_cls == BufClass::PAGEABLE;
+        st.unstage_bytes = recv_b;
+        // BCAST is an in-place op: its schedule reads the payload from
+        // RECV space (no SEND-space step), so the staged input must land
+        // in stage_recv as well — without this the staged root broadcasts
+        // an uninitialized buffer (caught by the e2e param-consistency
+        // check on the device engine).
+        if (req->Spec().op == CollOp::BCAST && s_host) {
+            LaunchCopy(st.stage_recv, st.stage_send, recv_b, base_s);
+            // re-fan-out: channel streams must order after this copy
+            // too, not only after the send staging
+            FanOutStream0(gc, st);
+        }
+    }
+    req->SetDeviceBuffers(s_host ? static_cast<const uint8_t*>(st.stage_send) : nullptr,
+                          r_host ? static_cast<uint8_t*>(st.stage_recv) : nullptr);
+    return s_host || r_host;
+}
+
+// Order the priority lane after the producers and any staging H2D:
+// both dependencies are carried by channel stream 0 at this point
+// (it waited on the compute stream above if that was busy, and the
+// staging copy was enqueued on it), so record a fresh event there
+// unconditionally — st.dep_event may not exist yet when the compute
+// stream was idle and no staging ran.
+void OrderPriorityLane(GroupComms& gc, DeviceReqState& st) {
+    RecordDep(st, gc.streams[0]);
+    HIP_CHECKD(hipStreamWaitEvent(gc.prio_stream, st.dep_event, 0));
+}
+
+// What one Start decided before it issues.
+struct IssueCtx {
+    hipStream_t base_s = nullptr;  // n=1: the compute stream (short) or stream 0
+    bool prio = false;             // everything rides the priority lane
+    bool p2p = false;              // IPC window transport
+    size_t nch = 1;                // channels chunks are dealt over
+};
+
+void IssueAll(CommRequest* req, GroupComms& gc, DeviceReqState& st, const IssueCtx& ic) {
+    auto& chunks = req->Chunks();
+    const size_t es = DtypeSize(req->Dtype());
+    const bool compressed = req->Compressed();
+    const bool use_schedule = req->UsesDeviceSchedule();
+    if (gc.comms.empty() && !ic.p2p) {
+        hipStream_t s0 = ic.base_s;
+        for (auto& ce : chunks) {
+            const uint8_t* sbase = req->SendBuf() + ce.elem_off * es;
+            uint8_t* rbase = req->RecvBuf() + ce.elem_off * es;
+            if (compressed) {
+                // quantize -> dequantize keeps the quantized
+                // collective's semantics (and error feedback) at n=1
+                IssueCompressed(req, ce, static_cast<uint8_t*>(st.tmp_dev), sbase, rbase,
+                                s0, [](uint8_t*, uint8_t*) {});
+            } else if (ce.sch.result.bytes && sbase != rbase) {
+                // NT copy kernel: measured faster than the blit path for
+                // large streams (docs/BENCHMARKS.md); buffers are device
+                // memory here (host users are staged above).
+                LaunchCopy(rbase + ce.sch.result.off, sbase,
+                           ce.sch.result.bytes, s0);
+            }
+        }
+        if (st.recv_staged) EnqueueUnstage(req, st, s0);
+        return;
+    }
+    size_t tmp_off = 0;
+    for (auto& ce : chunks) {
+        const size_t ch = ce.chunk_idx % ic.nch;
+        hipStream_t strm_ = ic.prio ? gc.prio_stream : gc.streams[ch];
+        uint8_t* tbase = static_cast<uint8_t*>(st.tmp_dev) + tmp_off;
+        // IPC window transport: every op walks its schedule; lane
+        // nlanes-1 is the priority lane.
+        const size_t lane = !ic.p2p ? 0 : ic.prio ? gc.p2p->Lanes() - 1 : ch;
+        ncclComm_t comm_ = ic.p2p ? nullptr : ic.prio ? gc.prio_comm : gc.comms[ch];
+        auto walk = [&](const uint8_t* sbase, uint8_t* rbase, uint8_t* scratch) {
+            if (ic.p2p) gc.p2p->IssueSchedule(req, ce, lane, strm_, sbase, rbase, scratch);
+            else IssueSchedule(req, ce, comm_, strm_, sbase, rbase, scratch);
+        };
+        if (compressed) {
+            // quantize -> compressed-domain ring -> dequantize (driver
+            // config 5: int8 allreduce / reduce-scatter of bf16/f32 grads)
+            IssueCompressed(req, ce, tbase, req->SendBuf(), req->RecvBuf(), strm_,
+                            [&](uint8_t* wire, uint8_t* scratch) { walk(wire, wire, scratch); });
+            tmp_off += ce.qplan.bytes;
+        } else if (ic.p2p || use_schedule) {
+            walk(req->SendBuf() + ce.elem_off * es, req->RecvBuf() + ce.elem_off * es, tbase);
+            tmp_off += ce.sch.tmp_bytes;
+        } else {
+            IssueFused(req, ce, comm_, strm_, st, tmp_off);
+            tmp_off += ce.sch.tmp_bytes;
+        }
+    }
+}
+
+// Issue eagerly, or (try_capture) capture the issue into a hipGraph, launch
+// it and keep it for replay; a capture that fails at either end falls back
+// to eager for good.
+void IssueOrCapture(CommRequest* req, GroupComms& gc, DeviceReqState& st,
+                    const IssueCtx& ic, bool try_capture) {
+    if (!try_capture) {
+        IssueAll(req, gc, st, ic);
+        return;
+    }
+    bool body_ok = true;
+    hipError_t ce0 = hipStreamBeginCapture(gc.streams[0],
+                                           hipStreamCaptureModeThreadLocal);
+    if (ce0 == hipSuccess) {
+        try {
+            IssueAll(req, gc, st, ic);
+        } catch (const std::exception&) {
+            body_ok = false;
+        }
+        hipGraph_t graph = nullptr;
+        hipError_t ce1 = hipStreamEndCapture(gc.streams[0], &graph);
+        if (body_ok && ce1 == hipSuccess && graph &&
+            hipGraphInstantiate(&st.graph_exec, graph, nullptr, nullptr, 0) ==
+                hipSuccess) {
+            (void)hipGraphDestroy(graph);
+            st.captured_sbuf = req->SendBuf();
+            st.captured_rbuf = req->RecvBuf();
+            HIP_CHECKD(hipGraphLaunch(st.graph_exec, gc.streams[0]));
+        } else {
+            // capture produced nothing executable -> run eagerly
+            (void)hipGetLastError();
+            if (graph) (void)hipGraphDestroy(graph);
+            st.graph_exec = nullptr;
+            st.graph_failed = true;
+            IssueAll(req, gc, st, ic);
+        }
+    } else {
+        (void)hipGetLastError();
+        st.graph_failed = true;
+        IssueAll(req, gc, st, ic);
+    }
+}
+
+// Completion events (outside any graph). Graph path + single-channel
+// path complete on stream 0; multi-channel records one per channel.
+void RecordCompletion(CommRequest* req, GroupComms& gc, DeviceReqState& st,
+                      const IssueCtx& ic) {
+    if (st.graph_exec || (gc.comms.empty() && !ic.p2p)) {
+        EnsureEvents(st, 1);
+        HIP_CHECKD(hipEventRecord(st.events[0],
+                                  st.graph_exec ? gc.streams[0] : ic.base_s));
+        return;
+    }
+    const size_t used = std::min(req->Chunks().size(), ic.nch);
+    EnsureEvents(st, used);
+    for (size_t ch = 0; ch < used; ++ch)
+        HIP_CHECKD(hipEventRecord(st.events[ch],
+                                  ic.prio ? gc.prio_stream : gc.streams[ch]));
+    if (st.recv_staged) {
+        // join all channels on stream 0, then stage the result out
+        for (size_t ch = 0; ch < used; ++ch)
+            HIP_CHECKD(hipStreamWaitEvent(gc.streams[0], st.events[ch], 0));
+        EnqueueUnstage(req, st, gc.streams[0]);
+        EnsureEvents(st, used + 1);
+        HIP_CHECKD(hipEventRecord(st.events[used], gc.streams[0]));
+    }
 }
 
 }  // namespace
@@ -788,8 +993,9 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st) {
             MLSL_THROW("p2p transport wait aborted (peer dead or timeout)");
         return DeviceFinishIfDone(req, st);
     }
-    const bool p2p = gc.p2p != nullptr;
-    if (gc.comms.empty() && gc.streams.empty() && !p2p) {
+    IssueCtx ic;
+    ic.p2p = gc.p2p != nullptr;
+    if (gc.comms.empty() && gc.streams.empty() && !ic.p2p) {
         hipStream_t s0;
         HIP_CHECKD(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking));
         gc.streams.push_back(s0);
@@ -799,151 +1005,25 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st) {
     // issue directly on the compute stream — same-stream ordering makes
     // the dep-event handshake (two extra HIP calls of the small-message
     // floor) unnecessary. Large messages keep the side stream for overlap.
-    const bool short_local = gc.comms.empty() && !p2p &&
+    const bool short_local = gc.comms.empty() && !ic.p2p &&
                              req->MessageBytes() <= cfg.max_short_msg;
-    hipStream_t base_s = short_local ? static_cast<hipStream_t>(rt->ComputeStream())
-                                     : gc.streams[0];
+    ic.base_s = short_local ? static_cast<hipStream_t>(rt->ComputeStream())
+                            : gc.streams[0];
     if (!short_local) {
-        // Order after the caller's compute stream: the producer kernels
-        // (e.g. torch backward on the default stream) must land before the
-        // collective reads the buffers. When the compute stream is idle
-        // (hipStreamQuery ~0.1 us) there is nothing to order against and
-        // the record+wait pair (~4.5 us on the legacy stream) is skipped.
-        hipStream_t comp = static_cast<hipStream_t>(rt->ComputeStream());
-        hipError_t q = hipStreamQuery(comp);
-        if (q != hipSuccess) {
-            (void)hipGetLastError();
-            if (!st.dep_event)
-                HIP_CHECKD(hipEventCreateWithFlags(&st.dep_event, hipEventDisableTiming));
-            HIP_CHECKD(hipEventRecord(st.dep_event, comp));
-            for (hipStream_t cs : gc.streams)
-                HIP_CHECKD(hipStreamWaitEvent(cs, st.dep_event, 0));
-        }
+        OrderAfterCompute(rt, gc, st);
+        if (ReplayGraph(req, gc, st)) return AllEventsDone(st);
     }
 
-    // hipGraph replay (MLSL_USE_GRAPHS): same request + same buffers ->
-    // launch the captured graph instead of re-enqueueing.
-    if (!short_local && st.graph_exec && req->SendBuf() == st.captured_sbuf &&
-        req->RecvBuf() == st.captured_rbuf) {
-        HIP_CHECKD(hipGraphLaunch(st.graph_exec, gc.streams[0]));
-        EnsureEvents(st, 1);
-        HIP_CHECKD(hipEventRecord(st.events[0], gc.streams[0]));
-        st.issued = true;
-        return AllEventsDone(st);
-    }
-
-    // Host-buffer staging (ReplaceIn analog): stage host buffers through
-    // persistent HBM so RCCL/kernels see device memory. Pageable memory
-    // bounces through a persistent PINNED buffer in chunks — the H2D DMA of
-    // chunk k overlaps the host memcpy of chunk k+1; already-pinned user
-    // buffers DMA directly. (Classified fresh every Start:
-    // hipPointerGetAttributes is ~0.3 us and a pointer-value cache would
-    // misclassify a freed-and-reallocated pointer.)
-    size_t send_b = 0, recv_b = 0;
-    IoBytes(req, &send_b, &recv_b);
-    const BufClass s_cls = send_b > 0 ? ClassifyPtr(req->UserSendBuf())
-                                      : BufClass::DEV;
-    const BufClass r_cls = recv_b > 0 ? ClassifyPtr(req->UserRecvBuf())
-                                      : BufClass::DEV;
-    const bool s_host = s_cls != BufClass::DEV;
-    const bool r_host = r_cls != BufClass::DEV;
-    st.recv_staged = r_host;
-    st.unstage_pending = false;
-    constexpr size_t kStageChunk = 32u << 20;
-    if (s_host) {
-        if (!st.stage_send || st.stage_send_bytes < send_b) {
-            if (st.stage_send) rt->FreeDevice(st.stage_send);
-            st.stage_send = rt->AllocDevice(send_b);
-            st.stage_send_bytes = send_b;
-        }
-        if (s_cls == BufClass::PINNED) {
-            HIP_CHECKD(hipMemcpyAsync(st.stage_send, req->UserSendBuf(), send_b,
-                                      hipMemcpyHostToDevice, base_s));
-        } else {
-            if (!st.pin_send || st.pin_send_bytes < send_b) {
-                if (st.pin_send) (void)hipHostFree(st.pin_send);
-                HIP_CHECKD(hipHostMalloc(&st.pin_send, send_b));
-                st.pin_send_bytes = send_b;
-            }
-            for (size_t off = 0; off < send_b; off += kStageChunk) {
-                const size_t n = std::min(kStageChunk, send_b - off);
-                HostStageCopy(static_cast<uint8_t*>(st.pin_send) + off,
-                              req->UserSendBuf() + off, n);
-                HIP_CHECKD(hipMemcpyAsync(
-                    static_cast<uint8_t*>(st.stage_send) + off,
-                    static_cast<uint8_t*>(st.pin_send) + off, n,
-                    hipMemcpyHostToDevice, base_s));
-            }
-        }
-        if (gc.streams.size() > 1) {
-            if (!st.dep_event)
-                HIP_CHECKD(hipEventCreateWithFlags(&st.dep_event,
-                                                   hipEventDisableTiming));
-            HIP_CHECKD(hipEventRecord(st.dep_event, gc.streams[0]));
-            for (size_t i = 1; i < gc.streams.size(); ++i)
-                HIP_CHECKD(hipStreamWaitEvent(gc.streams[i], st.dep_event, 0));
-        }
-    }
-    if (r_host) {
-        if (!st.stage_recv || st.stage_recv_bytes < recv_b) {
-            if (st.stage_recv) rt->FreeDevice(st.stage_recv);
-            st.stage_recv = rt->AllocDevice(recv_b);
-            st.stage_recv_bytes = recv_b;
-        }
-        if (r_cls == BufClass::PAGEABLE &&
-            (!st.pin_recv || st.pin_recv_bytes < recv_b)) {
-            if (st.pin_recv) (void)hipHostFree(st.pin_recv);
-            HIP_CHECKD(hipHostMalloc(&st.pin_recv, recv_b));
-            st.pin_recv_bytes = recv_b;
-        }
-        // Pageable: D2H lands in the pinned bounce; the final pinned->user
-        // memcpy runs host-side once the completion events fire.
-        st.unstage_pending = r_cls == BufClass::PAGEABLE;
-        st.unstage_bytes = recv_b;
-        // BCAST is an in-place op: its schedule reads the payload from
-        // RECV space (no SEND-space step), so the staged input must land
-        // in stage_recv as well — without this the staged root broadcasts
-        // an uninitialized buffer (caught by the e2e param-consistency
-        // check on the device engine).
-        if (req->Spec().op == CollOp::BCAST && s_host) {
-            LaunchCopy(st.stage_recv, st.stage_send, recv_b, base_s);
-            if (gc.streams.size() > 1) {
-                // re-fan-out: channel streams must order after this copy
-                // too, not only after the send staging
-                if (!st.dep_event)
-                    HIP_CHECKD(hipEventCreateWithFlags(&st.dep_event,
-                                                       hipEventDisableTiming));
-                HIP_CHECKD(hipEventRecord(st.dep_event, gc.streams[0]));
-                for (size_t i = 1; i < gc.streams.size(); ++i)
-                    HIP_CHECKD(hipStreamWaitEvent(gc.streams[i], st.dep_event, 0));
-            }
-        }
-    }
-    req->SetDeviceBuffers(s_host ? static_cast<const uint8_t*>(st.stage_send) : nullptr,
-                          r_host ? static_cast<uint8_t*>(st.stage_recv) : nullptr);
-    auto& chunks = req->Chunks();
-    const bool use_schedule = req->UsesDeviceSchedule();
-    const bool compressed = req->Compressed();
-    const bool prio = cfg.msg_priority &&
-                      (gc.prio_comm || (p2p && gc.prio_stream)) &&
-                      req->MessageBytes() >= cfg.msg_priority_threshold;
-    if (prio) {
-        // Order the priority lane after the producers and any staging H2D:
-        // both dependencies are carried by channel stream 0 at this point
-        // (it waited on the compute stream above if that was busy, and the
-        // staging copy was enqueued on it), so record a fresh event there
-        // unconditionally — st.dep_event may not exist yet when the compute
-        // stream was idle and no staging ran.
-        if (!st.dep_event)
-            HIP_CHECKD(hipEventCreateWithFlags(&st.dep_event, hipEventDisableTiming));
-        HIP_CHECKD(hipEventRecord(st.dep_event, gc.streams[0]));
-        HIP_CHECKD(hipStreamWaitEvent(gc.prio_stream, st.dep_event, 0));
-    }
+    const bool staged = StageIn(req, rt, gc, st, ic.base_s);
+    ic.prio = cfg.msg_priority &&
+              (gc.prio_comm || (ic.p2p && gc.prio_stream)) &&
+              req->MessageBytes() >= cfg.msg_priority_threshold;
+    if (ic.prio) OrderPriorityLane(gc, st);
 
     // Graph capture only when everything lands on ONE capturable stream:
     // no pageable staging, no priority lane, single channel.
-    const bool try_capture = cfg.use_graphs && !st.graph_failed && !s_host &&
-                             !r_host && !prio && !short_local && !p2p &&
+    const bool try_capture = cfg.use_graphs && !st.graph_failed && !staged &&
+                             !ic.prio && !short_local && !ic.p2p &&
                              GraphEligible(req, gc);
 
     // hipEvent device timing (MLSL_STATS): t0 on the stream that issues
@@ -952,150 +1032,13 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st) {
     if (st.timed) {
         if (!st.t0_event)
             HIP_CHECKD(hipEventCreateWithFlags(&st.t0_event, hipEventDefault));
-        HIP_CHECKD(hipEventRecord(st.t0_event, prio ? gc.prio_stream : base_s));
+        HIP_CHECKD(hipEventRecord(st.t0_event, ic.prio ? gc.prio_stream : ic.base_s));
     }
 
-    const size_t es = DtypeSize(req->Dtype());
-    const size_t nch = p2p ? std::max<size_t>(1, gc.streams.size())
-                           : (gc.comms.empty() ? 1 : gc.comms.size());
-    const size_t used = (gc.comms.empty() && !p2p)
-                            ? 1
-                            : std::min(chunks.size(), nch);
-
-    auto issue_all = [&]() {
-        if (gc.comms.empty() && !p2p) {
-            hipStream_t s0 = base_s;
-            for (auto& ce : chunks) {
-                const uint8_t* sbase = req->SendBuf() + ce.elem_off * es;
-                uint8_t* rbase = req->RecvBuf() + ce.elem_off * es;
-                if (compressed) {
-                    // quantize -> dequantize keeps the quantized
-                    // collective's semantics (and error feedback) at n=1
-                    const QuantScratch q =
-                        QuantLayout(req, ce, static_cast<uint8_t*>(st.tmp_dev));
-                    QuantPrologue(req, ce, q, sbase, s0);
-                    QuantEpilogue(req, ce, q, rbase, s0);
-                } else if (ce.sch.result.bytes && sbase != rbase) {
-                    // NT copy kernel: measured faster than the blit path for
-                    // large streams (docs/BENCHMARKS.md); buffers are device
-                    // memory here (host users are staged above).
-                    LaunchCopy(rbase + ce.sch.result.off, sbase,
-                               ce.sch.result.bytes, s0);
-                }
-            }
-            if (st.recv_staged)
-                HIP_CHECKD(hipMemcpyAsync(
-                    st.unstage_pending ? st.pin_recv
-                                       : static_cast<void*>(req->UserRecvBuf()),
-                    st.stage_recv, recv_b, hipMemcpyDeviceToHost, s0));
-            return;
-        }
-        size_t tmp_off = 0;
-        for (auto& ce : chunks) {
-            const size_t ch = ce.chunk_idx % nch;
-            hipStream_t strm_ = prio ? gc.prio_stream : gc.streams[ch];
-            if (p2p) {
-                // IPC window transport: every op walks its schedule; lane
-                // nlanes-1 is the priority lane.
-                const size_t lane = prio ? gc.p2p->Lanes() - 1 : ch;
-                uint8_t* tbase = static_cast<uint8_t*>(st.tmp_dev) + tmp_off;
-                if (compressed) {
-                    const QuantScratch q = QuantLayout(req, ce, tbase);
-                    QuantPrologue(req, ce, q, req->SendBuf(), strm_);
-                    gc.p2p->IssueSchedule(req, ce, lane, strm_, q.wire, q.wire,
-                                          q.scratch);
-                    QuantEpilogue(req, ce, q, req->RecvBuf(), strm_);
-                    tmp_off += q.bytes;
-                } else {
-                    gc.p2p->IssueSchedule(req, ce, lane, strm_,
-                                          req->SendBuf() + ce.elem_off * es,
-                                          req->RecvBuf() + ce.elem_off * es,
-                                          tbase);
-                    tmp_off += ce.sch.tmp_bytes;
-                }
-                continue;
-            }
-            ncclComm_t comm_ = prio ? gc.prio_comm : gc.comms[ch];
-            uint8_t* tbase = static_cast<uint8_t*>(st.tmp_dev) + tmp_off;
-            if (compressed) {
-                // quantize -> compressed-domain ring -> dequantize (driver
-                // config 5: int8 allreduce / reduce-scatter of bf16/f32 grads)
-                const QuantScratch q = QuantLayout(req, ce, tbase);
-                QuantPrologue(req, ce, q, req->SendBuf(), strm_);
-                IssueSchedule(req, ce, comm_, strm_, q.wire, q.wire, q.scratch);
-                QuantEpilogue(req, ce, q, req->RecvBuf(), strm_);
-                tmp_off += q.bytes;
-            } else if (use_schedule) {
-                IssueSchedule(req, ce, comm_, strm_,
-                              req->SendBuf() + ce.elem_off * es,
-                              req->RecvBuf() + ce.elem_off * es, tbase);
-                tmp_off += ce.sch.tmp_bytes;
-            } else {
-                IssueFused(req, ce, comm_, strm_, st, tmp_off);
-                tmp_off += ce.sch.tmp_bytes;
-            }
-        }
-    };
-
-    if (try_capture) {
-        bool body_ok = true;
-        hipError_t ce0 = hipStreamBeginCapture(gc.streams[0],
-                                               hipStreamCaptureModeThreadLocal);
-        if (ce0 == hipSuccess) {
-            try {
-                issue_all();
-            } catch (const std::exception&) {
-                body_ok = false;
-            }
-            hipGraph_t graph = nullptr;
-            hipError_t ce1 = hipStreamEndCapture(gc.streams[0], &graph);
-            if (body_ok && ce1 == hipSuccess && graph &&
-                hipGraphInstantiate(&st.graph_exec, graph, nullptr, nullptr, 0) ==
-                    hipSuccess) {
-                (void)hipGraphDestroy(graph);
-                st.captured_sbuf = req->SendBuf();
-                st.captured_rbuf = req->RecvBuf();
-                HIP_CHECKD(hipGraphLaunch(st.graph_exec, gc.streams[0]));
-            } else {
-                // capture produced nothing executable -> run eagerly
-                (void)hipGetLastError();
-                if (graph) (void)hipGraphDestroy(graph);
-                st.graph_exec = nullptr;
-                st.graph_failed = true;
-                issue_all();
-            }
-        } else {
-            (void)hipGetLastError();
-            st.graph_failed = true;
-            issue_all();
-        }
-    } else {
-        issue_all();
-    }
-
-    // Completion events (outside any graph). Graph path + single-channel
-    // path complete on stream 0; multi-channel records one per channel.
-    if (st.graph_exec || (gc.comms.empty() && !p2p)) {
-        EnsureEvents(st, 1);
-        HIP_CHECKD(hipEventRecord(st.events[0],
-                                  st.graph_exec ? gc.streams[0] : base_s));
-    } else {
-        EnsureEvents(st, used);
-        for (size_t ch = 0; ch < used; ++ch)
-            HIP_CHECKD(hipEventRecord(st.events[ch],
-                                      prio ? gc.prio_stream : gc.streams[ch]));
-        if (st.recv_staged) {
-            // join all channels on stream 0, then stage the result out
-            for (size_t ch = 0; ch < used; ++ch)
-                HIP_CHECKD(hipStreamWaitEvent(gc.streams[0], st.events[ch], 0));
-            HIP_CHECKD(hipMemcpyAsync(
-                st.unstage_pending ? st.pin_recv
-                                   : static_cast<void*>(req->UserRecvBuf()),
-                st.stage_recv, recv_b, hipMemcpyDeviceToHost, gc.streams[0]));
-            EnsureEvents(st, used + 1);
-            HIP_CHECKD(hipEventRecord(st.events[used], gc.streams[0]));
-        }
-    }
+    ic.nch = ic.p2p ? std::max<size_t>(1, gc.streams.size())
+                    : (gc.comms.empty() ? 1 : gc.comms.size());
+    IssueOrCapture(req, gc, st, ic, try_capture);
+    RecordCompletion(req, gc, st, ic);
     st.issued = true;
     return DeviceFinishIfDone(req, st);
 }

@@ -44,7 +44,7 @@ struct DeviceReqState {
     // D2H landed in pin_recv; the final pinned->user memcpy runs on the
     // host after the completion events fire.
     bool unstage_pending = false;
-    size_t unstage_bytes = 0;
+    size_t unstage_bytes = 0;   // of the staged recv buffer, bounced or not
     // hipGraph replay (MLSL_USE_GRAPHS): the issue sequence captured once,
     // replayed on subsequent Starts with the same buffers.
     hipGraphExec_t graph_exec = nullptr;

@@ -1,0 +1,42 @@
+#include "quant_plan.hpp"
+
+namespace mlsl {
+
+QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t count,
+                        size_t elem_size) {
+    auto al16 = [](size_t x) { return (x + 15) & ~size_t(15); };
+    const BufRef& res = sch.result;
+    MLSL_CHECK(sch.quant_block > 0 && nseg > 0 && (nseg == 1 || me < nseg),
+               "not a compressed chunk's schedule");
+    MLSL_CHECK((res.space == Space::TMP) == (nseg > 1),
+               "a compressed result is in TMP exactly for a reduce-scatter on "
+               "more than one rank");
+    QuantPlan p;
+    p.block = sch.quant_block;
+    p.count = count;
+    p.nseg = nseg;
+    p.seg_bytes = count * elem_size;
+    p.seg_wire = sch.wire_bytes / nseg;
+    p.scratch_off = al16(nseg * p.seg_wire);
+    p.err_off = p.scratch_off + al16(sch.tmp_bytes);
+    p.bytes = p.err_off + al16(nseg * p.seg_bytes);
+    if (sch.fan_in > 0) {
+        MLSL_CHECK(sch.fan_in + 1 == nseg && nseg <= kQuantRsDirectMaxRanks,
+                   "one-shot fan-in takes one wire per rank, 8 at the most");
+        p.finish = QuantFinish::SUMN;
+        p.nwires = static_cast<int>(nseg);
+        for (size_t r = 0; r < nseg; ++r)
+            p.wire_off[r] = r == me ? me * p.seg_wire
+                                    : p.scratch_off + res.off + (r < me ? r : r - 1) * p.seg_wire;
+    } else if (res.space == Space::TMP) {
+        p.finish = QuantFinish::SUM2;
+        p.nwires = 2;
+        p.wire_off[0] = p.scratch_off + res.off;
+        p.wire_off[1] = me * p.seg_wire;
+    } else {
+        p.wire_off[0] = res.off;
+    }
+    return p;
+}
+
+}  // namespace mlsl

@@ -1,0 +1,55 @@
+// Plan of one compressed (int8-quantized) chunk: where its wire, schedule
+// scratch and error-feedback residual live, how the send buffer is cut into
+// quantized segments, and which kernel finishes which wires. Built once per
+// chunk at Setup; the host executor (request.cpp) and every device executor
+// (device_comm.cpp) read it and derive none of this themselves.
+//
+// Layout from the chunk base, each region padded to 16 bytes so that the
+// vectorized quant kernels' fast paths apply (wire blocks are block + 8
+// bytes, so raw offsets are only 8-byte aligned):
+//   [0, nseg * seg_wire)        wire: the quantized image of the whole send
+//                               buffer; the schedule's SEND and RECV refs
+//                               address it
+//   [scratch_off, + tmp_bytes)  the schedule's TMP space
+//   [err_off, + nseg * seg_bytes)  residual, one element per send element
+//
+// The prologue quantizes send segment j (seg_bytes apart in the send buffer
+// and the residual) into wire segment j (seg_wire apart), each on a block
+// grid of its own, before anything writes the recv buffer: the two may alias
+// anywhere. Then the schedule runs, then the finish writes `count` elements:
+//   DEQUANT  allreduce, and any op on a group of one: dequantize wire_off[0]
+//   SUM2     ring reduce-scatter: the partial sum that arrived last
+//            (wire_off[0], in TMP) plus this rank's own segment (wire_off[1]),
+//            one fused kernel
+//   SUMN     one-shot reduce-scatter (fan_in > 0): the fan_in arrived wires
+//            and the own segment in ascending group rank, own at position
+//            `me`, summed once by the N-way kernel
+// Host only: no HIP, no Context.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../core/types.hpp"
+#include "schedule.hpp"
+
+namespace mlsl {
+
+enum class QuantFinish : uint8_t { DEQUANT, SUM2, SUMN };
+
+struct QuantPlan {
+    size_t block = 0, count = 0;       // wire block elems; elements per segment (= result elems)
+    size_t nseg = 1;                   // send segments (N for reduce-scatter, else 1)
+    size_t seg_bytes = 0, seg_wire = 0;   // strides in send buffer/residual, and in the wire
+    size_t scratch_off = 0, err_off = 0, bytes = 0;   // the wire region is at 0
+    QuantFinish finish = QuantFinish::DEQUANT;
+    int nwires = 1;                    // 1, 2, or fan_in + 1
+    size_t wire_off[kQuantRsDirectMaxRanks] = {};   // in the order the finish sums them
+};
+
+// `sch` is a *Units schedule of rank `me`; `count` elements of `elem_size`
+// bytes per segment. Throws where the schedule does not fit a finish.
+QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t count,
+                        size_t elem_size);
+
+}  // namespace mlsl

@@ -169,16 +169,6 @@ bool CommRequest::UsesDeviceSchedule() const {
            spec_.op == CollOp::ALLREDUCE && group_->Size() > 1 && !Compressed();
 }
 
-size_t CommRequest::WireBytesFor(const ChunkExec& ce) const {
-    return ce.sch.wire_bytes;
-}
-
-size_t CommRequest::ResidualElems() const {
-    return spec_.op == CollOp::REDUCE_SCATTER
-               ? spec_.count * static_cast<size_t>(group_->Size())
-               : spec_.count;
-}
-
 size_t CommRequest::MessageBytes() const {
     const size_t es = DtypeSize(dtype_);
     switch (spec_.op) {
@@ -404,6 +394,10 @@ void CommRequest::BuildChunks() {
                 ce.sch = BuildSendRecvList(gr, gs, spec_.pairs, dtype_);
                 break;
         }
+        if (Compressed())
+            ce.qplan = MakeQuantPlan(
+                ce.sch, spec_.op == CollOp::REDUCE_SCATTER ? static_cast<size_t>(gs) : 1,
+                static_cast<size_t>(gr), spec_.count, es);
         total_tmp_bytes_ += ce.sch.tmp_bytes;
         // Phase byte 0xFF is reserved for edge-sequenced p2p tags (PairTag);
         // a schedule reaching phase 255 (ring allreduce at 129+ ranks,
@@ -422,16 +416,8 @@ void CommRequest::Setup() {
         dev_ = std::make_unique<DeviceState>();
         DeviceSetupRequest(this, *dev_);
     } else {
-        for (auto& ce : chunks_) {
-            size_t t = ce.sch.tmp_bytes;
-            if (Compressed()) {
-                // [wire][schedule scratch][error-feedback residual]
-                const size_t wire = WireBytesFor(ce);
-                const size_t err = ResidualElems() * DtypeSize(dtype_);
-                t = wire + ce.sch.tmp_bytes + err;
-            }
-            ce.tmp.assign(t, 0);
-        }
+        for (auto& ce : chunks_)
+            ce.tmp.assign(Compressed() ? ce.qplan.bytes : ce.sch.tmp_bytes, 0);
     }
     setup_done_ = true;
 }
@@ -569,20 +555,10 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
         const uint8_t* sbase = sbuf_ + ce.elem_off * es;
         uint8_t* rbase = rbuf_ + ce.elem_off * es;
         uint8_t* wire = ce.tmp.data();                         // compressed only
-        const size_t wire_bytes = compressed ? WireBytesFor(ce) : 0;
-        // Reduce-scatter quantizes each of its N send segments on a block
-        // grid of its own; the allreduce is one segment.
-        const size_t nseg = spec_.op == CollOp::REDUCE_SCATTER
-                                ? static_cast<size_t>(group_->Size()) : 1;
-        const size_t seg_wire = wire_bytes / nseg;
+        const QuantPlan& qp = ce.qplan;                        // (quant_plan.hpp)
         auto ptr = [&](const BufRef& b) -> uint8_t* {
-            if (compressed) {
-                switch (b.space) {
-                    case Space::SEND: return wire + b.off;
-                    case Space::RECV: return wire + b.off;
-                    case Space::TMP: return ce.tmp.data() + wire_bytes + b.off;
-                }
-            }
+            if (compressed)
+                return wire + (b.space == Space::TMP ? qp.scratch_off : 0) + b.off;
             switch (b.space) {
                 case Space::SEND: return const_cast<uint8_t*>(sbase) + b.off;
                 case Space::RECV: return rbase + b.off;
@@ -592,24 +568,21 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
         };
         if (compressed && !ce.prologue_done) {
             // quantize user send (+ residual) into the wire
-            // The whole send buffer is quantized before the first byte of
-            // the recv buffer is written, so the two may alias anywhere.
-            uint8_t* err = ce.tmp.data() + wire_bytes + ce.sch.tmp_bytes;
-            for (size_t j = 0; j < nseg; ++j) {
-                const uint8_t* seg = sbase + j * spec_.count * es;
-                uint8_t* seg_err = err + j * spec_.count * es;
+            for (size_t j = 0; j < qp.nseg; ++j) {
+                const uint8_t* seg = sbase + j * qp.seg_bytes;
+                uint8_t* seg_err = wire + qp.err_off + j * qp.seg_bytes;
                 if (plugin_) {
                     // reference ABI: dtype enum {INT8=0,F16=1,F32=2,F64=3},
                     // comp_ratio = input-elem-bytes (int8 wire), method DFP=1
                     const int sdt = dtype_ == DataType::F32 ? 2
                                     : dtype_ == DataType::F64 ? 3 : 1;
                     int rc = plugin_->quant(const_cast<uint8_t*>(seg),
-                                            wire + j * seg_wire, spec_.count,
+                                            wire + j * qp.seg_wire, qp.count,
                                             seg_err, sdt, DtypeSize(dtype_), 1);
                     MLSL_CHECK(rc == 0, "quant plugin compress failed");
                 } else {
-                    HostQuantize(seg, seg_err, wire + j * seg_wire, spec_.count,
-                                 qparams_.block_elems, dtype_, true);
+                    HostQuantize(seg, seg_err, wire + j * qp.seg_wire, qp.count, qp.block,
+                                 dtype_, true);
                 }
             }
             ce.prologue_done = true;
@@ -678,37 +651,35 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
             if (ce.cur_phase >= ce.sch.num_phases) {
                 ce.finished = true;
                 if (compressed) {
-                    // Reduce-scatter on more than one rank: the partial sum
-                    // that arrived last and this rank's own wire segment
-                    // still have to meet. The plugin ABI has no fused hook,
-                    // so there the sum is requantized into the arrival slot.
-                    // The one-shot schedule leaves fan_in wires in TMP, one
-                    // per peer in ascending rank order; they and the own
-                    // segment are summed in that order, once.
-                    uint8_t* res = ptr(ce.sch.result);
-                    const uint8_t* own =
-                        nseg > 1 ? wire + static_cast<size_t>(group_->MyIdx()) * seg_wire
-                                 : nullptr;
-                    if (ce.sch.fan_in > 0) {
-                        const void* wires[kQuantRsDirectMaxRanks];
-                        const size_t me = static_cast<size_t>(group_->MyIdx());
-                        for (size_t r = 0; r < nseg; ++r)
-                            wires[r] = r == me ? own : res + (r < me ? r : r - 1) * seg_wire;
-                        HostQuantSumDequantN(wires, static_cast<int>(nseg), rbase,
-                                             spec_.count, qparams_.block_elems, dtype_);
-                    } else if (plugin_) {
-                        int rc = own ? plugin_->reduce_sum(
-                                           own, res, seg_wire / qparams_.WireBlockBytes())
+                    // The plugin ABI has no fused hook: there a SUM2 finish
+                    // requantizes the sum into the arrival slot first. (The
+                    // one-shot schedule is refused with a plugin at Setup.)
+                    const void* wires[kQuantRsDirectMaxRanks];
+                    for (int k = 0; k < qp.nwires; ++k) wires[k] = wire + qp.wire_off[k];
+                    if (plugin_) {
+                        uint8_t* res = wire + qp.wire_off[0];
+                        int rc = qp.finish == QuantFinish::SUM2
+                                     ? plugin_->reduce_sum(
+                                           wires[1], res,
+                                           qp.seg_wire / qparams_.WireBlockBytes())
                                      : 0;
                         MLSL_CHECK(rc == 0, "quant plugin reduce failed");
-                        rc = plugin_->dequant(res, rbase, spec_.count);
+                        rc = plugin_->dequant(res, rbase, qp.count);
                         MLSL_CHECK(rc == 0, "quant plugin decompress failed");
-                    } else if (own) {
-                        HostQuantSumDequant(res, own, rbase, spec_.count,
-                                            qparams_.block_elems, dtype_);
                     } else {
-                        HostDequantize(res, rbase, spec_.count,
-                                       qparams_.block_elems, dtype_);
+                        switch (qp.finish) {
+                            case QuantFinish::SUMN:
+                                HostQuantSumDequantN(wires, qp.nwires, rbase, qp.count,
+                                                     qp.block, dtype_);
+                                break;
+                            case QuantFinish::SUM2:
+                                HostQuantSumDequant(wires[0], wires[1], rbase, qp.count,
+                                                    qp.block, dtype_);
+                                break;
+                            case QuantFinish::DEQUANT:
+                                HostDequantize(wires[0], rbase, qp.count, qp.block, dtype_);
+                                break;
+                        }
                     }
                 }
             }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../core/types.hpp"
+#include "quant_plan.hpp"
 #include "schedule.hpp"
 
 namespace mlsl {
@@ -65,6 +66,7 @@ struct OpSpec {
 // generalized (eplib/allreduce_pr.c:69-343).
 struct ChunkExec {
     Schedule sch;
+    QuantPlan qplan;          // compressed requests only; filled by BuildChunks
     size_t elem_off = 0;      // element offset of this chunk in the message
     size_t chunk_idx = 0;
     bool prologue_done = false;   // compressed path: quantize ran
@@ -122,12 +124,6 @@ class CommRequest {
     // True when the device executor will walk the schedule (custom ring/RHD
     // over ncclSend/Recv) instead of the fused RCCL op.
     bool UsesDeviceSchedule() const;
-    // Compressed-path layout inside each chunk's tmp:
-    // [wire W][schedule scratch][error-feedback residual]. The wire is the
-    // quantized image of the whole send buffer; the residual has one element
-    // per send element (N * count for REDUCE_SCATTER).
-    size_t WireBytesFor(const ChunkExec& ce) const;
-    size_t ResidualElems() const;
 
     // ---- lifecycle ----
     void Setup();                         // compile schedules, size scratch

@@ -60,14 +60,11 @@ struct Schedule {
     // then in wire bytes (unit = quant_block + 8).
     size_t quant_block = 0;
     // quant_block > 0: bytes of the wire image of the user's send buffer,
-    // which the executor keeps in front of the schedule scratch and which
-    // SEND/RECV refs address. Equals result.bytes for the allreduce; the
-    // reduce-scatter's wire holds N segments and its result only one.
+    // which SEND/RECV refs address (N equal segments for a reduce-scatter).
     size_t wire_bytes = 0;
-    // >0 (one-shot quantized reduce-scatter only): this many wires arrived,
-    // one per equal TMP slot in ascending peer-rank order; the result is
-    // their sum with this rank's own SEND segment, taken by the executor's
-    // N-way sum-dequantize epilogue. 0 everywhere else.
+    // >0 (one-shot quantized reduce-scatter only): `result` names this many
+    // equal TMP slots, one arrived wire each, in ascending peer-rank order.
+    // What the executors make of both: quant_plan.hpp.
     size_t fan_in = 0;
     // Direct (one-shot) allreduce shape: phase 1 is "send TMP(0,B) to all
     // peers, receive each peer's TMP slot, reduce all into RECV(0,B)" —

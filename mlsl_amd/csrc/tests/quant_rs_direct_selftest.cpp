@@ -1,12 +1,16 @@
-// Pure-host test of the one-shot (direct) quantized reduce-scatter, built
-// with ASan/UBSan and run by pytest (tests/test_quant_rs_direct_cpu.py):
+// Pure-host test of the one-shot (direct) quantized reduce-scatter and of
+// the plan of every compressed chunk, built with ASan/UBSan and run by pytest
+// (tests/test_quant_rs_direct_cpu.py):
 //   - BuildReduceScatterDirectUnits for worlds 1..9: the simulator accepts
 //     the schedules (every send has a matching receive of the same size),
 //     the receive slots are disjoint and cover tmp_bytes, and wire segment
 //     `to` goes to rank `to` and lands in the slot the epilogue reads;
+//   - MakeQuantPlan for the allreduce, ring and direct reduce-scatter unit
+//     schedules of worlds 1..9, every rank, against formulas written out
+//     here: layout, finish and wire table;
 //   - HostQuantize -> the exchange walked by hand -> HostQuantSumDequantN
-//     for worlds 2..8 against the sum of the dequantized wires in rank order
-//     with one fmaf per wire.
+//     for worlds 2..8, all inside one plan-sized buffer per rank, against the
+//     sum of the dequantized wires in rank order with one fmaf per wire.
 // Exit 0 = PASS.
 #include <algorithm>
 #include <cmath>
@@ -15,6 +19,7 @@
 #include <vector>
 
 #include "../comm/quant.hpp"
+#include "../comm/quant_plan.hpp"
 #include "../comm/schedule.hpp"
 
 using namespace mlsl;
@@ -37,9 +42,6 @@ static std::vector<Schedule> Build(int N, size_t units, size_t block) {
         sch[r] = BuildReduceScatterDirectUnits(r, N, units, block + 8, block);
     return sch;
 }
-
-// slot of peer `from` in rank r's TMP: ascending rank order, r left out
-static size_t SlotOf(int from, int r) { return static_cast<size_t>(from < r ? from : from - 1); }
 
 static void TestSchedule(int N, size_t units, size_t block) {
     const size_t segB = units * (block + 8);
@@ -75,7 +77,8 @@ static void TestSchedule(int N, size_t units, size_t block) {
                        st.send.off == static_cast<size_t>(st.send_peer) * segB,
                    "N=%d r=%d: send to %d reads off %zu", N, r, st.send_peer, st.send.off);
             EXPECT(st.recv.space == Space::TMP && st.recv.bytes == segB &&
-                       st.recv.off == SlotOf(st.recv_peer, r) * segB,
+                       // ascending rank order with r left out
+                       st.recv.off == (st.recv_peer - (st.recv_peer > r)) * segB,
                    "N=%d r=%d: recv from %d lands at %zu", N, r, st.recv_peer, st.recv.off);
             ++sent_to[st.send_peer];
             ++got_from[st.recv_peer];
@@ -105,6 +108,79 @@ static void TestSchedule(int N, size_t units, size_t block) {
     }
 }
 
+static size_t Al16(size_t x) { return (x + 15) / 16 * 16; }
+
+enum class Algo { ALLREDUCE, RING, DIRECT };
+
+// Every field of every rank's plan against the layout and finish rules
+// written out here (quant_plan.hpp states them; nothing below calls the plan
+// for an expectation).
+static void TestPlan(Algo algo, int N, size_t units, size_t block, size_t es) {
+    const size_t U = block + 8, segB = units * U;
+    const size_t count = units * block - 3;   // a tail block: units = ceil(count / block)
+    for (int r = 0; r < N; ++r) {
+        const size_t me = static_cast<size_t>(r);
+        const Schedule sch =
+            algo == Algo::ALLREDUCE ? BuildAllReduceRingUnits(r, N, units, U, block)
+            : algo == Algo::RING    ? BuildReduceScatterUnits(r, N, units, U, block)
+                                    : BuildReduceScatterDirectUnits(r, N, units, U, block);
+        const size_t nseg = algo == Algo::ALLREDUCE ? 1 : static_cast<size_t>(N);
+        QuantPlan p;
+        bool threw = false;
+        try {
+            p = MakeQuantPlan(sch, nseg, me, count, es);
+        } catch (const std::exception&) {
+            threw = true;
+        }
+        const int a = static_cast<int>(algo);
+        EXPECT(threw == (algo == Algo::DIRECT && N > 8), "plan algo=%d N=%d r=%d: threw=%d",
+               a, N, r, threw);
+        if (threw) continue;
+        // scratch: the allreduce ring's largest segment, two ring slots (one
+        // at world 2), one slot per peer for direct
+        const size_t tmp = N == 1                 ? 0
+                           : algo == Algo::ALLREDUCE ? (units + N - 1) / N * U
+                           : algo == Algo::RING      ? std::min(2, N - 1) * segB
+                                                     : (N - 1) * segB;
+        const size_t wire_end = nseg * segB, scratch = Al16(wire_end);
+        const size_t err = scratch + Al16(tmp), err_end = err + nseg * count * es;
+        EXPECT(p.block == block && p.count == count && p.nseg == nseg &&
+                   p.seg_bytes == count * es && p.seg_wire == segB,
+               "plan algo=%d N=%d r=%d: nseg %zu seg_wire %zu", a, N, r, p.nseg, p.seg_wire);
+        EXPECT(p.scratch_off == scratch && p.err_off == err && p.bytes == Al16(err_end),
+               "plan algo=%d N=%d r=%d: offsets %zu %zu %zu", a, N, r, p.scratch_off,
+               p.err_off, p.bytes);
+        EXPECT(p.scratch_off % 16 == 0 && p.err_off % 16 == 0 && p.bytes % 16 == 0,
+               "plan algo=%d N=%d r=%d: unaligned region", a, N, r);
+        EXPECT(wire_end <= p.scratch_off && p.scratch_off + sch.tmp_bytes <= p.err_off &&
+                   sch.tmp_bytes == tmp && err_end <= p.bytes,
+               "plan algo=%d N=%d r=%d: regions overlap", a, N, r);
+        std::vector<size_t> want;
+        QuantFinish fin = QuantFinish::DEQUANT;
+        if (algo == Algo::ALLREDUCE || N == 1) {
+            want = {0};
+        } else if (algo == Algo::RING) {
+            fin = QuantFinish::SUM2;   // arrived partial sum first, own segment second
+            want = {scratch + (N % 2) * segB, me * segB};
+        } else {
+            fin = QuantFinish::SUMN;   // ascending rank; peers fill the slots in that order
+            for (size_t q = 0; q < nseg; ++q)
+                want.push_back(q == me ? me * segB : scratch + (q - (q > me)) * segB);
+        }
+        EXPECT(p.finish == fin && p.nwires == static_cast<int>(want.size()),
+               "plan algo=%d N=%d r=%d: finish %d nwires %d", a, N, r,
+               static_cast<int>(p.finish), p.nwires);
+        for (size_t k = 0; k < want.size() && k < 8; ++k) {
+            EXPECT(p.wire_off[k] == want[k], "plan algo=%d N=%d r=%d: wire %zu at %zu", a, N, r,
+                   k, p.wire_off[k]);
+            // a whole wire inside the wire region or inside the scratch
+            const size_t lo = p.wire_off[k], hi = lo + (nseg > 1 ? segB : wire_end);
+            EXPECT(hi <= wire_end || (lo >= p.scratch_off && hi <= p.scratch_off + tmp),
+                   "plan algo=%d N=%d r=%d: wire %zu outside its region", a, N, r, k);
+        }
+    }
+}
+
 static uint16_t ToBf16(float f) {
     uint32_t u;
     std::memcpy(&u, &f, 4);
@@ -117,11 +193,13 @@ static void TestExchange(int N, size_t count, size_t block, DataType dt) {
     const size_t units = (count + block - 1) / block;
     const size_t segB = units * (block + 8);
     std::vector<Schedule> sch = Build(N, units, block);
+    // one plan-sized buffer per rank: wire, scratch and residual inside it
+    std::vector<QuantPlan> plan(N);
+    std::vector<std::vector<uint8_t>> buf(N);
     // inputs: a different magnitude per rank, so the block scales differ
-    std::vector<std::vector<uint8_t>> wire(N), tmp(N);
     uint32_t lcg = 12345u + static_cast<uint32_t>(N);
     for (int r = 0; r < N; ++r) {
-        std::vector<uint8_t> in(N * count * es), err(N * count * es, 0);
+        std::vector<uint8_t> in(N * count * es);
         for (size_t i = 0; i < N * count; ++i) {
             lcg = lcg * 1664525u + 1013904223u;
             const float v = (static_cast<float>(lcg >> 8) / 8388608.f - 1.f) * (1.f + r);
@@ -131,11 +209,12 @@ static void TestExchange(int N, size_t count, size_t block, DataType dt) {
                 std::memcpy(&in[i * 2], &h, 2);
             }
         }
-        wire[r].assign(N * segB, 0);
-        tmp[r].assign(sch[r].tmp_bytes, 0xAB);
-        for (int j = 0; j < N; ++j)
-            HostQuantize(in.data() + j * count * es, err.data() + j * count * es,
-                         wire[r].data() + j * segB, count, block, dt, true);
+        const QuantPlan& p = plan[r] = MakeQuantPlan(sch[r], N, r, count, es);
+        buf[r].assign(p.bytes, 0xAB);
+        std::memset(buf[r].data() + p.err_off, 0, p.nseg * p.seg_bytes);
+        for (size_t j = 0; j < p.nseg; ++j)
+            HostQuantize(in.data() + j * p.seg_bytes, buf[r].data() + p.err_off + j * p.seg_bytes,
+                         buf[r].data() + j * p.seg_wire, p.count, p.block, dt, true);
     }
     // the exchange by hand: each send lands where the receiver's step of the
     // same phase points
@@ -143,21 +222,20 @@ static void TestExchange(int N, size_t count, size_t block, DataType dt) {
         for (const Step& st : sch[r].steps)
             for (const Step& pt : sch[st.send_peer].steps)
                 if (pt.phase == st.phase && pt.recv_peer == r)
-                    std::memcpy(tmp[st.send_peer].data() + pt.recv.off,
-                                wire[r].data() + st.send.off, st.send.bytes);
+                    std::memcpy(buf[st.send_peer].data() + plan[st.send_peer].scratch_off +
+                                    pt.recv.off,
+                                buf[r].data() + st.send.off, st.send.bytes);
     for (int r = 0; r < N; ++r) {
-        // pointer table in ascending rank order, own segment at position r
+        // the plan's wire table: ascending rank order, own segment at r
         const void* wires[8];
-        for (int p = 0; p < N; ++p)
-            wires[p] = p == r ? wire[r].data() + r * segB
-                              : tmp[r].data() + sch[r].result.off + SlotOf(p, r) * segB;
+        for (int k = 0; k < plan[r].nwires; ++k) wires[k] = buf[r].data() + plan[r].wire_off[k];
         std::vector<uint8_t> out(count * es, 0xCD), want(count * es);
-        HostQuantSumDequantN(wires, N, out.data(), count, block, dt);
+        HostQuantSumDequantN(wires, plan[r].nwires, out.data(), count, block, dt);
         for (size_t i = 0; i < count; ++i) {
             float acc = 0.f;
             for (int p = 0; p < N; ++p) {
                 // rank p's wire of segment r, straight from where p quantized it
-                const uint8_t* wb = wire[p].data() + r * segB + (i / block) * (block + 8);
+                const uint8_t* wb = buf[p].data() + r * segB + (i / block) * (block + 8);
                 float scale;
                 std::memcpy(&scale, wb, 4);
                 acc = std::fmaf(static_cast<float>(static_cast<int8_t>(wb[8 + i % block])),
@@ -198,6 +276,15 @@ int main() {
         TestSchedule(N, 1, 256);
         TestSchedule(N, 5, 128);
     }
+    for (Algo algo : {Algo::ALLREDUCE, Algo::RING, Algo::DIRECT})
+        for (int N = 1; N <= 9; ++N)
+            for (size_t es : {2, 4}) {
+                TestPlan(algo, N, 1, 256, es);
+                TestPlan(algo, N, 5, 128, es);
+                // 3 x 5 x 264 = 3960 is no multiple of 16: padding behind the wire
+                // at world 3, and behind a one-slot scratch at world 2
+                TestPlan(algo, N, 5, 256, es);
+            }
     for (int N = 2; N <= 8; ++N)
         for (DataType dt : {DataType::F32, DataType::BF16}) {
             TestExchange(N, 1003, 128, dt);

@@ -151,6 +151,13 @@ def test_quant_reduce_scatter_multislot():
 
 
 @requires_gpu
+def test_quant_reduce_scatter_numpy_buffers():
+    # pageable send and recv buffers: staged through HBM around the
+    # compressed issue path, the pinned bounce copied out at completion
+    w.run_ranks("rs_check", 2, device="numpy", inplace=[False])
+
+
+@requires_gpu
 def test_quant_reduce_scatter_world1():
     w.run_ranks("rs_check", 1, device=True)
 

@@ -126,5 +126,12 @@ def test_direct_reduce_scatter_multislot():
 
 
 @requires_gpu
+def test_direct_reduce_scatter_numpy_buffers():
+    # pageable send and recv buffers: staged through HBM around the
+    # compressed issue path, the pinned bounce copied out at completion
+    wd.run_ranks("direct_check", 2, device="numpy", inplace=[False])
+
+
+@requires_gpu
 def test_sharded_optimizer_int8_direct():
     wd.run_ranks("direct_sharded_optimizer", 2, device=True)

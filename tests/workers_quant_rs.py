@@ -5,7 +5,7 @@ arithmetic of a world-2 quantized reduce-scatter after the quantization
 itself), a launcher of the shape of tests/mp.py for this module's workers,
 and the workers. The workers run unchanged on the TCP host transport (numpy
 buffers) and on the device transport with every rank on GPU 0 (torch
-buffers); QRS_DEVICE picks.
+buffers, or pageable numpy buffers that the engine stages); QRS_DEVICE picks.
 
 Run as: python -m tests.workers_quant_rs <worker> '<json kwargs>'
 """
@@ -98,18 +98,25 @@ def rel_l2(got_f64, want_f64):
 
 # ---- launcher --------------------------------------------------------------
 
+def qrs_device(device):
+    """QRS_DEVICE for run_ranks' `device`: False is the TCP transport, True
+    the device transport with torch buffers, "numpy" the device transport
+    with pageable numpy buffers, which the engine stages."""
+    return {False: "cpu", True: "gpu", "numpy": "gpu-numpy"}[device]
+
+
 def run_ranks(worker, world, device=False, timeout=120, extra_env=None, **kwargs):
     """tests.workers_quant_rs.<worker>(**kwargs) in `world` processes, on
-    the TCP transport or (device=True) all on GPU 0. Every process gets
-    `timeout` seconds; the first to exceed it takes all ranks down. Raises
-    on a nonzero exit; returns the stdouts."""
+    the TCP transport or (device=True or "numpy") all on GPU 0. Every process
+    gets `timeout` seconds; the first to exceed it takes all ranks down.
+    Raises on a nonzero exit; returns the stdouts."""
     port = free_port()
     procs = []
     for r in range(world):
         env = dict(os.environ)
         env.update({"RANK": str(r), "WORLD_SIZE": str(world),
                     "MASTER_ADDR": "127.0.0.1", "MLSL_PORT": str(port),
-                    "PYTHONPATH": REPO, "QRS_DEVICE": "gpu" if device else "cpu"})
+                    "PYTHONPATH": REPO, "QRS_DEVICE": qrs_device(device)})
         if device:
             env.pop("MLSL_TRANSPORT", None)
             env["MLSL_TIMEOUT"] = "90"
@@ -153,8 +160,9 @@ def ensure_plugin():
 # ---- workers ---------------------------------------------------------------
 
 class _Bufs:
-    """numpy arrays on the host transport, torch tensors on GPU 0; bf16
-    travels as 16-bit integers either way."""
+    """numpy arrays on the host transport (and where QRS_DEVICE keeps them
+    on the device transport), torch tensors on GPU 0 otherwise; bf16 travels
+    as 16-bit integers either way."""
 
     def __init__(self):
         self.gpu = os.environ.get("QRS_DEVICE") == "gpu"
@@ -206,18 +214,18 @@ def _reduce_scatter(mx, bufs, d, rank, size, dtype, count, inplace, starts=1):
     return outs
 
 
-def _configs(shapes, dtypes=("f32", "bf16")):
-    return [(dt, c, b, ip) for dt in dtypes for c, b in shapes for ip in (False, True)]
+def _configs(shapes, dtypes=("f32", "bf16"), inplace=(False, True)):
+    return [(dt, c, b, ip) for dt in dtypes for c, b in shapes for ip in inplace]
 
 
-def rs_check(shapes=None, dtypes=("f32", "bf16")):
+def rs_check(shapes=None, dtypes=("f32", "bf16"), inplace=(False, True)):
     """World 2: every output element is one of the three candidates built
     from the reference-quantized wires of the two ranks' segments. Larger
     worlds: relative L2 error against the float64 sum below 0.05, and not
     the exact sum. World 1: dequantize(quantize(x)) bit for bit."""
     mx, bufs, rank, size = _init()
     d = mx.Distribution(size, 1)
-    for dtype, count, block, inplace in _configs(shapes or COLL_SHAPES, dtypes):
+    for dtype, count, block, inplace in _configs(shapes or COLL_SHAPES, dtypes, inplace):
         mx.set_quant_params(block)
         out = _reduce_scatter(mx, bufs, d, rank, size, dtype, count, inplace)[0]
         what = (size, dtype, count, block, "inplace" if inplace else "outofplace")

@@ -134,7 +134,7 @@ def exact_segment(rank, size, count, dtype):
 
 def run_ranks(worker, world, device=False, timeout=120, extra_env=None, **kwargs):
     """tests.workers_quant_rs_direct.<worker>(**kwargs) in `world` processes,
-    on the TCP transport or (device=True) all on GPU 0. Every process gets
+    on the TCP transport or (device=True or "numpy") all on GPU 0. Every process gets
     `timeout` seconds; the first to exceed it takes all ranks down. Raises on
     a nonzero exit; returns the stdouts."""
     port = free_port()
@@ -144,7 +144,7 @@ def run_ranks(worker, world, device=False, timeout=120, extra_env=None, **kwargs
         env.pop("MLSL_QUANT_RS_ALGO", None)
         env.update({"RANK": str(r), "WORLD_SIZE": str(world),
                     "MASTER_ADDR": "127.0.0.1", "MLSL_PORT": str(port),
-                    "PYTHONPATH": REPO, "QRS_DEVICE": "gpu" if device else "cpu"})
+                    "PYTHONPATH": REPO, "QRS_DEVICE": w.qrs_device(device)})
         if device:
             env.pop("MLSL_TRANSPORT", None)
             env["MLSL_TIMEOUT"] = "90"
@@ -210,7 +210,8 @@ def _reduce_scatter(mx, bufs, d, rank, size, dtype, count, inplace, algo, starts
     return outs
 
 
-def direct_check(shapes=None, dtypes=("f32", "bf16"), algo="direct", compare_ring=True):
+def direct_check(shapes=None, dtypes=("f32", "bf16"), algo="direct", compare_ring=True,
+                 inplace=(False, True)):
     """The first start of a direct request equals `expected_segment` bit for
     bit on every rank (world 1: dequantize(quantize(x))). From world 3 up
     the ring, on the same inputs, is further from the float64 sum: it
@@ -218,7 +219,8 @@ def direct_check(shapes=None, dtypes=("f32", "bf16"), algo="direct", compare_rin
     MLSL_QUANT_RS_ALGO=direct in the environment."""
     mx, bufs, rank, size = w._init()
     d = mx.Distribution(size, 1)
-    for dtype, count, block, inplace in w._configs(shapes or w.COLL_SHAPES, dtypes):
+    for dtype, count, block, inplace in w._configs(shapes or w.COLL_SHAPES, dtypes,
+                                                   inplace):
         mx.set_quant_params(block)
         out = _reduce_scatter(mx, bufs, d, rank, size, dtype, count, inplace, algo)[0]
         what = (size, dtype, count, block, "inplace" if inplace else "outofplace")
