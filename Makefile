@@ -133,6 +133,31 @@ $(ASAN_QRS_DIRECT): mlsl_amd/csrc/tests/quant_rs_direct_selftest.cpp mlsl_amd/cs
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -ldl -o $@
 
+# The quantized all-gather under ASan/UBSan: its schedule (matching, slots,
+# what each send reads), its plan (one segment in, N out, no residual), and
+# the host codec walked through the exchange by hand inside plan-sized
+# buffers, assigned and accumulated. Pure host C++, like the target above.
+ASAN_QAG := $(BUILD)/quant_ag_selftest_asan
+
+asan-quant-ag: $(ASAN_QAG)
+	$(ASAN_QAG)
+
+$(ASAN_QAG): mlsl_amd/csrc/tests/quant_ag_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/comm/quant_plan.cpp mlsl_amd/csrc/core/log.cpp
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $^ -pthread -ldl -o $@
+
+# What a compressed all-gather request refuses at Setup(), through the C++
+# classes and the library as built (no sanitizer; world 1 over TCP).
+QAG_REQUEST := $(BUILD)/quant_ag_request_selftest
+
+quant-ag-request: $(QAG_REQUEST)
+
+$(QAG_REQUEST): mlsl_amd/csrc/tests/quant_ag_request_selftest.cpp $(LIB)
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 $< -Lmlsl_amd -lmlsl_amd \
+	    -Wl,-rpath,'$$ORIGIN/../mlsl_amd' -pthread -o $@
+
 # Full-stack ASan: the API selftest (planner+engine+mesh, TCP world
 # matrix) host-compiled with g++ + ASan/UBSan; device kernels stubbed.
 ASAN_API := $(BUILD)/api_selftest_asan

@@ -13,7 +13,13 @@ chain of kernels the ring runs on one segment, N-2 quant_accum plus one
 quant_sum_dequant (--melems elements, block 256, f32 and bf16).
 --mode reduce_scatter: quantized (ring, and direct up to 8 ranks) against
 exact reduce-scatter of --melems elements per rank (launch with
-benchmarks/mp_run.py for N>1)."""
+benchmarks/mp_run.py for N>1).
+--mode dequant_segments_ab: single-GPU A/B of the quantized all-gather's
+finish, dequantize_segments at 2, 4 and 8 segments, assigned against
+per-segment and flat dequantize calls and accumulated against dequantize into
+scratch plus reduce_ (--melems elements in all, block 256, f32 and bf16).
+--mode all_gather: quantized all-gather, assign and accumulate, against the
+exact all-gather of --melems elements in all (mp_run.py for N>1)."""
 import argparse
 import json
 import os
@@ -169,11 +175,174 @@ def sum_dequant_n_ab(args):
             del out
 
 
+def dequant_segments_ab(args):
+    """One line of JSON per (nseg, dtype): the segmented dequantize of the
+    quantized all-gather against what the unchanged kernels offer, --melems
+    elements in all. Assign: `segments` against `separate` (nseg dequantize
+    calls, one per segment) and `flat` (one dequantize call over the whole
+    wire, legal here because segments are whole blocks). Accumulate:
+    `segments_acc` against `scratch_reduce` (one flat dequantize into scratch,
+    then reduce_ of scratch into out). Timing as in sum_dequant_ab: host clock
+    around `iters` launch+sync pairs, interleaved rounds; `separate` pays the
+    call overhead nseg times, `scratch_reduce` twice. GB/s against the least
+    bytes the kernel must move: the wire in and one element out, plus one
+    element in when accumulating."""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("dequant_segments_ab measures GPU kernels: no GPU found")
+    from mlsl_amd import ops
+    torch.cuda.set_device(0)
+    total, block = args.melems << 20, 256
+    torch.manual_seed(0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters
+
+    for nseg in (2, 4, 8):
+        count = total // nseg
+        assert count % block == 0
+        seg_wire = ops.wire_bytes(count, block)
+        wire = torch.empty(nseg * seg_wire, dtype=torch.uint8, device="cuda")
+        for j in range(nseg):
+            v = torch.randn(count, dtype=torch.float32, device="cuda") * (1.0 + j)
+            ops.quantize(v, wire[j * seg_wire:(j + 1) * seg_wire], count, block=block,
+                         dtype="f32")
+            del v
+        for dtype, tdt, es in (("f32", torch.float32, 4), ("bf16", torch.bfloat16, 2)):
+            out = torch.zeros(total, dtype=tdt, device="cuda")
+            scratch = torch.empty(total, dtype=tdt, device="cuda")
+
+            def separate():
+                for j in range(nseg):
+                    ops.dequantize(wire[j * seg_wire:(j + 1) * seg_wire],
+                                   out[j * count:(j + 1) * count], count, block=block,
+                                   dtype=dtype)
+
+            variants = {
+                "segments": lambda: ops.dequantize_segments(wire, out, count, nseg,
+                                                            block=block, dtype=dtype),
+                "separate": separate,
+                "flat": lambda: ops.dequantize(wire, out, total, block=block, dtype=dtype),
+                "segments_acc": lambda: ops.dequantize_segments(
+                    wire, out, count, nseg, block=block, dtype=dtype, accumulate=True),
+                "scratch_reduce": lambda: (
+                    ops.dequantize(wire, scratch, total, block=block, dtype=dtype),
+                    ops.reduce_(out, scratch, total, dtype=dtype, op="sum")),
+                "call_overhead": lambda: ops.dequantize_segments(wire, out, block, 1,
+                                                                 block=block, dtype=dtype),
+            }
+            # same bits before anything is timed
+            ref = torch.empty_like(out)
+            ops.dequantize(wire, ref, total, block=block, dtype=dtype)
+            variants["segments"]()
+            assert torch.equal(out.view(torch.uint8), ref.view(torch.uint8))
+            for fn in variants.values():
+                for _ in range(args.warmup):
+                    fn()
+            times = {k: [] for k in variants}
+            for _ in range(args.rounds):
+                for k, fn in variants.items():
+                    out.zero_()    # accumulating variants must not run off to inf
+                    times[k].append(timed(fn))
+            res = {"config": "dequant-segments-ab", "nseg": nseg, "dtype": dtype,
+                   "melems": args.melems, "block": block, "iters": args.iters,
+                   "rounds": args.rounds}
+            for k, v in times.items():
+                res[f"{k}_us_median"] = round(_median(v) * 1e6, 1)
+                res[f"{k}_us_min"] = round(min(v) * 1e6, 1)
+            wbytes = nseg * seg_wire
+            res["assign_min_bytes_per_elem"] = round((wbytes + total * es) / total, 3)
+            res["acc_min_bytes_per_elem"] = round((wbytes + 2 * total * es) / total, 3)
+            res["segments_GBps"] = round((wbytes + total * es) /
+                                         _median(times["segments"]) / 1e9, 1)
+            res["flat_GBps"] = round((wbytes + total * es) / _median(times["flat"]) / 1e9, 1)
+            res["segments_acc_GBps"] = round((wbytes + 2 * total * es) /
+                                             _median(times["segments_acc"]) / 1e9, 1)
+            res["segments_over_separate"] = round(_median(times["segments"]) /
+                                                  _median(times["separate"]), 3)
+            res["segments_over_flat"] = round(_median(times["segments"]) /
+                                              _median(times["flat"]), 3)
+            res["acc_over_scratch_reduce"] = round(_median(times["segments_acc"]) /
+                                                   _median(times["scratch_reduce"]), 3)
+            print(json.dumps(res), flush=True)
+            del out, scratch, ref
+        del wire
+
+
+def all_gather_bench(args):
+    """Quantized all-gather, assign and accumulate, against the exact
+    all-gather of the same elements: --melems elements in all, 1/world of
+    them from each rank (launch with benchmarks/mp_run.py for N>1).
+    --exact-only times the exact request alone."""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("all_gather mode measures the device transport: no GPU found")
+    import mlsl_amd as mx
+    mx.init()
+    rank, size = mx.rank(), mx.world_size()
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)) % torch.cuda.device_count())
+    es = 2 if args.dtype == "bf16" else 4
+    tdt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    count = (args.melems << 20) // size // 256 * 256
+    torch.manual_seed(1 + rank)
+    send = (torch.randn(count, dtype=torch.float32, device="cuda") * 0.01).to(tdt)
+    d = mx.Distribution(size, 1)
+    reqs = [("exact", mx.PersistentRequest(d, "all_gather", count, dtype=args.dtype,
+                                           group="data"))]
+    if not args.exact_only:
+        reqs += [("int8_assign", mx.PersistentRequest(
+                      d, "all_gather", count, dtype=args.dtype, group="data",
+                      quantized=True)),
+                 ("int8_accumulate", mx.PersistentRequest(
+                      d, "all_gather", count, dtype=args.dtype, group="data",
+                      quantized=True, accumulate=True))]
+    results, outs = {}, {}
+    for name, req in reqs:
+        recv = torch.zeros(size * count, dtype=tdt, device="cuda")
+
+        def run():
+            req.start(send, recv)
+            req.wait()
+
+        for _ in range(args.warmup):
+            run()
+        recv.zero_()
+        torch.cuda.synchronize()
+        d.barrier("global")
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            run()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / args.iters
+        results[name] = {"ms": round(dt * 1e3, 3),
+                         "algbw_GBps": round(size * count * es / dt / 1e9, 2)}
+        outs[name] = recv
+    res = {"config": "int8-quantized-all-gather", "dtype": args.dtype,
+           "total_mib": size * count * es >> 20, "world": size,
+           **{f"{k}_{kk}": vv for k, v in results.items() for kk, vv in v.items()}}
+    if not args.exact_only:
+        x = outs["exact"].float()
+        res["assign_max_abs_err"] = round((outs["int8_assign"].float() - x).abs().max().item(), 8)
+        res["half_step"] = round(x.abs().max().item() / 254.0, 8)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    for _, req in reqs:
+        req.destroy()
+    mx.finalize()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="allreduce",
-                    choices=["allreduce", "reduce_scatter", "sum_dequant_ab",
-                             "sum_dequant_n_ab"])
+                    choices=["allreduce", "reduce_scatter", "all_gather", "sum_dequant_ab",
+                             "sum_dequant_n_ab", "dequant_segments_ab"])
+    ap.add_argument("--exact-only", action="store_true",
+                    help="all_gather mode: time the exact request alone")
     ap.add_argument("--melems", type=int, default=64,
                     help="Mi elements (per rank) for the reduce-scatter and kernel A/B modes")
     ap.add_argument("--rounds", type=int, default=5)
@@ -187,6 +356,10 @@ def main():
         return sum_dequant_ab(args)
     if args.mode == "sum_dequant_n_ab":
         return sum_dequant_n_ab(args)
+    if args.mode == "dequant_segments_ab":
+        return dequant_segments_ab(args)
+    if args.mode == "all_gather":
+        return all_gather_bench(args)
     rs = args.mode == "reduce_scatter"
 
     use_cuda = False

@@ -384,11 +384,23 @@ class PersistentRequest:
     at construction, start/wait/test are allocation-free."""
 
     def __init__(self, dist, kind, count, dtype="f32", op="sum", group="global",
-                 quantized=False, algo=None):
+                 quantized=False, algo=None, accumulate=False):
         """algo: quantized reduce_scatter only. None takes MLSL_QUANT_RS_ALGO
         (ring unless set); "ring" or "direct" names it. See
-        mlsl_persistent_reduce_scatter_quantized_algo."""
+        mlsl_persistent_reduce_scatter_quantized_algo.
+        accumulate: quantized all_gather only. False assigns recv =
+        dequantize(wire) per segment; True adds it to what recv holds, one
+        fma per element. Either way every rank, the contributor included,
+        decodes the same wire, so recv ends bit-identical across ranks, and
+        nothing is carried from one start to the next (no error feedback).
+        See mlsl_persistent_all_gather_quantized."""
         import ctypes as _c
+        if accumulate and (kind != "all_gather" or not quantized):
+            raise ValueError('accumulate=True is the accumulating finish of the '
+                             'quantized all_gather: it needs kind="all_gather" and '
+                             'quantized=True')
+        if quantized and kind == "all_to_all":
+            raise ValueError('quantized=True is not supported for kind="all_to_all"')
         if algo is not None:
             if kind != "reduce_scatter" or not quantized:
                 raise ValueError('algo= selects the quantized reduce_scatter\'s '
@@ -409,6 +421,8 @@ class PersistentRequest:
                 c_void_p, c_size_t, c_int, c_int, c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_all_gather.argtypes = [c_void_p, c_size_t, c_int, c_int,
                                                      P(c_void_p)]
+            L.mlsl_persistent_all_gather_quantized.argtypes = [
+                c_void_p, c_size_t, c_int, c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_all_to_all.argtypes = [c_void_p, c_size_t, c_int, c_int,
                                                      P(c_void_p)]
             L.mlsl_request_start.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -418,8 +432,8 @@ class PersistentRequest:
             for n in ("mlsl_persistent_all_reduce", "mlsl_persistent_reduce_scatter",
                       "mlsl_persistent_reduce_scatter_quantized",
                       "mlsl_persistent_reduce_scatter_quantized_algo",
-                      "mlsl_persistent_all_gather", "mlsl_persistent_all_to_all",
-                      "mlsl_request_start", "mlsl_request_wait", "mlsl_request_test",
+                      "mlsl_persistent_all_gather", "mlsl_persistent_all_gather_quantized",
+                      "mlsl_persistent_all_to_all", "mlsl_request_start", "mlsl_request_wait", "mlsl_request_test",
                       "mlsl_request_destroy"):
                 getattr(L, n).restype = c_int
             L._persist_declared = True
@@ -444,6 +458,12 @@ class PersistentRequest:
                       else L.mlsl_persistent_reduce_scatter)
                 check(fn(dist._h, count, DTYPE[dtype], REDOP[op], GROUP[group],
                          ctypes.byref(h)))
+        elif kind == "all_gather" and quantized:
+            # int8 wire, no error feedback; raises for anything but f32/bf16
+            # rather than running the exact collective instead
+            check(L.mlsl_persistent_all_gather_quantized(
+                dist._h, count, DTYPE[dtype], GROUP[group], 1 if accumulate else 0,
+                ctypes.byref(h)))
         elif kind == "all_gather":
             check(L.mlsl_persistent_all_gather(dist._h, count, DTYPE[dtype],
                                                GROUP[group], ctypes.byref(h)))

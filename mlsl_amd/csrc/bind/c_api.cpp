@@ -311,6 +311,23 @@ int mlsl_persistent_all_gather(mlsl_distribution d, size_t send_count, mlsl_data
     C_CATCH
 }
 
+int mlsl_persistent_all_gather_quantized(mlsl_distribution d, size_t send_count,
+                                         mlsl_data_type dt, mlsl_group g, int accumulate,
+                                         mlsl_request* out) {
+    C_TRY
+    // never fall back to an exact all-gather behind the caller's back
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized all_gather supports f32/bf16 only");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddAllGather(send_count);
+    r->SetCompression(Compression::QUANT_INT8,
+                      Environment::GetEnv().GetQuantizationParams());
+    r->SetQuantAccumulate(accumulate != 0);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
 int mlsl_persistent_all_to_all(mlsl_distribution d, size_t send_count, mlsl_data_type dt,
                                mlsl_group g, mlsl_request* out) {
     C_TRY CommRequest* r = NewPersistent(d, g, dt);

@@ -138,6 +138,14 @@ int mlsl_hip_quant_sum_dequant_n(const void* const* wires, int nwires, void* out
     OPS_CATCH
 }
 
+int mlsl_hip_dequantize_segments(const void* wire, size_t nseg, void* out, size_t count,
+                                 size_t block, int dt, int accumulate) {
+    OPS_TRY LaunchDequantizeSegments(wire, nseg, out, count, block,
+                                     static_cast<DataType>(dt), accumulate != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
 // Host codec (comm/quant.cpp) on host pointers: same wire format and the
 // same argument order as the device ops above.
 int mlsl_host_quantize(const void* in, void* err, void* wire, size_t count,
@@ -170,6 +178,13 @@ int mlsl_host_quant_sum_dequant_n(const void* const* wires, int nwires, void* ou
                                   size_t count, size_t block, int dt) {
     OPS_TRY HostQuantSumDequantN(wires, nwires, out, count, block,
                                  static_cast<DataType>(dt));
+    OPS_CATCH
+}
+
+int mlsl_host_dequantize_segments(const void* wire, size_t nseg, void* out, size_t count,
+                                  size_t block, int dt, int accumulate) {
+    OPS_TRY HostDequantizeSegments(wire, nseg, out, count, block,
+                                   static_cast<DataType>(dt), accumulate != 0);
     OPS_CATCH
 }
 

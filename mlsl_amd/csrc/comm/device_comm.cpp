@@ -441,6 +441,14 @@ void IoBytes(CommRequest* req, size_t* send_b, size_t* recv_b) {
     *recv_b = r;
 }
 
+// Whether the request's finish reads the recv buffer as well as writing it.
+bool RecvIsInput(CommRequest* req) {
+    if (!req->Compressed()) return false;
+    for (const auto& ce : req->Chunks())
+        if (ce.qplan.finish == QuantFinish::SCATTER && ce.qplan.accumulate) return true;
+    return false;
+}
+
 // Issue one chunk through the fused RCCL op set.
 void IssueFused(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
                 DeviceReqState& st, size_t tmp_off) {
@@ -626,7 +634,8 @@ void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t
 }
 
 // One compressed chunk whose plan regions (quant_plan.hpp) start at `base`:
-// quantize every send segment, residual alongside; let `walk(wire, scratch)`
+// quantize every send segment where the plan says, residual alongside if it
+// has one; let `walk(wire, scratch)`
 // run the schedule over the wire; finish into rbuf. `walk` is the only thing
 // the executors differ in: nothing at n=1, the IPC window walker, or the
 // RCCL one.
@@ -636,8 +645,10 @@ void IssueCompressed(CommRequest* req, const ChunkExec& ce, uint8_t* base,
     const QuantPlan& p = ce.qplan;
     const DataType dt = req->Dtype();
     for (size_t j = 0; j < p.nseg; ++j)
-        LaunchQuantize(sbuf + j * p.seg_bytes, base + p.err_off + j * p.seg_bytes,
-                       base + j * p.seg_wire, p.count, p.block, dt, true, s);
+        LaunchQuantize(sbuf + j * p.seg_bytes,
+                       p.residual ? base + p.err_off + j * p.seg_bytes : nullptr,
+                       base + (p.send_seg + j) * p.seg_wire, p.count, p.block, dt,
+                       p.residual, s);
     walk(base, base + p.scratch_off);
     const void* wires[kQuantRsDirectMaxRanks];
     for (int k = 0; k < p.nwires; ++k) wires[k] = base + p.wire_off[k];
@@ -650,6 +661,10 @@ void IssueCompressed(CommRequest* req, const ChunkExec& ce, uint8_t* base,
             break;
         case QuantFinish::DEQUANT:
             LaunchDequantize(wires[0], rbuf, p.count, p.block, dt, s);
+            break;
+        case QuantFinish::SCATTER:
+            LaunchDequantizeSegments(wires[0], p.out_segs, rbuf, p.count, p.block, dt,
+                                     p.accumulate, s);
             break;
     }
 }
@@ -818,6 +833,28 @@ bool StageIn(CommRequest* req, HipRuntime* rt, GroupComms& gc, DeviceReqState& s
             LaunchCopy(st.stage_recv, st.stage_send, recv_b, base_s);
             // re-fan-out: channel streams must order after this copy
             // too, not only after the send staging
+            FanOutStream0(gc, st);
+        }
+        // An accumulating finish (quantized all-gather) READS recv: the
+        // user's values have to be in stage_recv before it runs. Pinned
+        // memory DMAs directly; pageable memory bounces through pin_recv in
+        // chunks as the send side does (the D2H of the result lands there
+        // only after everything issued below).
+        if (RecvIsInput(req)) {
+            if (r_cls == BufClass::PINNED) {
+                HIP_CHECKD(hipMemcpyAsync(st.stage_recv, req->UserRecvBuf(), recv_b,
+                                          hipMemcpyHostToDevice, base_s));
+            } else {
+                for (size_t off = 0; off < recv_b; off += kStageChunk) {
+                    const size_t n = std::min(kStageChunk, recv_b - off);
+                    HostStageCopy(static_cast<uint8_t*>(st.pin_recv) + off,
+                                  req->UserRecvBuf() + off, n);
+                    HIP_CHECKD(hipMemcpyAsync(
+                        static_cast<uint8_t*>(st.stage_recv) + off,
+                        static_cast<uint8_t*>(st.pin_recv) + off, n,
+                        hipMemcpyHostToDevice, base_s));
+                }
+            }
             FanOutStream0(gc, st);
         }
     }

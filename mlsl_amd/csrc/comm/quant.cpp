@@ -185,6 +185,39 @@ void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_
     }
 }
 
+void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t count,
+                            size_t block, DataType dt, bool accumulate) {
+    CheckQuantBlock(block, "HostDequantizeSegments");
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW("segmented dequantize supports f32/bf16 only");
+    MLSL_CHECK(nseg >= 1, "segmented dequantize takes at least one segment");
+    const size_t nblocks = (count + block - 1) / block;
+    const size_t seg_wire = nblocks * (block + 8);
+    for (size_t seg = 0; seg < nseg; ++seg) {
+        // every segment has a block grid of its own: a partial last block is
+        // followed by the next segment's block 0, not by the rest of a block
+        const uint8_t* w = static_cast<const uint8_t*>(wire) + seg * seg_wire;
+        for (size_t blk = 0; blk < nblocks; ++blk) {
+            const size_t base = seg * count + blk * block;
+            const size_t n = std::min(block, count - blk * block);
+            const uint8_t* wb = w + blk * (block + 8);
+            float s;
+            std::memcpy(&s, wb, 4);
+            const int8_t* p = reinterpret_cast<const int8_t*>(wb + 8);
+            for (size_t i = 0; i < n; ++i) {
+                const float q = static_cast<float>(p[i]);
+                if (dt == DataType::F32) {
+                    float* o = static_cast<float*>(out) + base + i;
+                    *o = accumulate ? std::fmaf(q, s, *o) : q * s;
+                } else {
+                    uint16_t* o = static_cast<uint16_t*>(out) + base + i;
+                    *o = F32B(accumulate ? std::fmaf(q, s, Bf16F(*o)) : q * s);
+                }
+            }
+        }
+    }
+}
+
 const QuantPluginApi* LoadQuantPlugin(const QuantParams& qp) {
     if (qp.lib_path.empty()) return nullptr;
     static std::mutex mu;

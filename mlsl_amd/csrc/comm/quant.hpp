@@ -35,6 +35,14 @@ void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
 // LaunchQuantSumDequantN computes.
 void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
                           size_t block, DataType dt);
+// The finish of the quantized all-gather: `wire` holds nseg segment wires of
+// QuantWireBytes(count, block) bytes each, every one on a block grid of its
+// own, and segment j goes to out[j * count, (j + 1) * count): assigned as
+// HostDequantize does it, or with `accumulate` as out = fmaf(q, scale, out)
+// in float, rounded once into the element type. Any nseg >= 1; the wire is
+// not written. Bit for bit what LaunchDequantizeSegments computes.
+void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t count,
+                            size_t block, DataType dt, bool accumulate);
 
 // dlopen'd compression plugin (reference quant/quant.c ABI — Intel
 // DL-comp style). Loaded once per lib_path; used by the HOST compressed

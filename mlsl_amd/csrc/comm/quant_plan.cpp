@@ -3,22 +3,39 @@
 namespace mlsl {
 
 QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t count,
-                        size_t elem_size) {
+                        size_t elem_size, QuantGather gather) {
     auto al16 = [](size_t x) { return (x + 15) & ~size_t(15); };
     const BufRef& res = sch.result;
     MLSL_CHECK(sch.quant_block > 0 && nseg > 0 && (nseg == 1 || me < nseg),
                "not a compressed chunk's schedule");
-    MLSL_CHECK((res.space == Space::TMP) == (nseg > 1),
-               "a compressed result is in TMP exactly for a reduce-scatter on "
-               "more than one rank");
     QuantPlan p;
     p.block = sch.quant_block;
     p.count = count;
-    p.nseg = nseg;
     p.seg_bytes = count * elem_size;
     p.seg_wire = sch.wire_bytes / nseg;
     p.scratch_off = al16(nseg * p.seg_wire);
     p.err_off = p.scratch_off + al16(sch.tmp_bytes);
+    if (gather != QuantGather::NONE) {
+        // one send segment in, quantized into this rank's place in the wire
+        // with no residual; nseg segments out
+        MLSL_CHECK(res.space != Space::TMP && res.off == 0 &&
+                       res.bytes == sch.wire_bytes && sch.fan_in == 0 &&
+                       sch.tmp_bytes == 0,
+                   "a compressed all-gather's result is the whole wire");
+        p.nseg = 1;
+        p.send_seg = me;
+        p.residual = false;
+        p.out_segs = nseg;
+        p.finish = QuantFinish::SCATTER;
+        p.accumulate = gather == QuantGather::ACCUMULATE;
+        p.wire_off[0] = 0;
+        p.bytes = p.err_off;
+        return p;
+    }
+    MLSL_CHECK((res.space == Space::TMP) == (nseg > 1),
+               "a compressed result is in TMP exactly for a reduce-scatter on "
+               "more than one rank");
+    p.nseg = nseg;
     p.bytes = p.err_off + al16(nseg * p.seg_bytes);
     if (sch.fan_in > 0) {
         MLSL_CHECK(sch.fan_in + 1 == nseg && nseg <= kQuantRsDirectMaxRanks,

@@ -11,12 +11,15 @@
 //                               buffer; the schedule's SEND and RECV refs
 //                               address it
 //   [scratch_off, + tmp_bytes)  the schedule's TMP space
-//   [err_off, + nseg * seg_bytes)  residual, one element per send element
+//   [err_off, + nseg * seg_bytes)  residual, one element per send element;
+//                               absent (0 bytes) where `residual` is false
 //
 // The prologue quantizes send segment j (seg_bytes apart in the send buffer
-// and the residual) into wire segment j (seg_wire apart), each on a block
-// grid of its own, before anything writes the recv buffer: the two may alias
-// anywhere. Then the schedule runs, then the finish writes `count` elements:
+// and the residual) into wire segment send_seg + j (seg_wire apart), each on
+// a block grid of its own and with the residual only where `residual` says
+// so, before anything writes the recv buffer: the two may alias anywhere.
+// Then the schedule runs, then the finish writes `count` elements, or
+// out_segs * count for SCATTER:
 //   DEQUANT  allreduce, and any op on a group of one: dequantize wire_off[0]
 //   SUM2     ring reduce-scatter: the partial sum that arrived last
 //            (wire_off[0], in TMP) plus this rank's own segment (wire_off[1]),
@@ -24,6 +27,15 @@
 //   SUMN     one-shot reduce-scatter (fan_in > 0): the fan_in arrived wires
 //            and the own segment in ascending group rank, own at position
 //            `me`, summed once by the N-way kernel
+//   SCATTER  all-gather: one send segment in, quantized into wire segment
+//            `me`; the whole wire (wire_off[0] = 0) is out_segs segments,
+//            rank j's at j * seg_wire, and the segmented dequantize writes
+//            segment j to recv + j * seg_bytes, or adds it there with one fma
+//            per element when `accumulate`. The own segment takes the same
+//            path from its own wire, so recv comes out bit-identical on all
+//            ranks. No residual: an error carried from one start to the next
+//            suits gradient sums; on gathered values it would add one
+//            start's rounding error to the next start's unrelated data.
 // Host only: no HIP, no Context.
 #pragma once
 
@@ -35,11 +47,17 @@
 
 namespace mlsl {
 
-enum class QuantFinish : uint8_t { DEQUANT, SUM2, SUMN };
+enum class QuantFinish : uint8_t { DEQUANT, SUM2, SUMN, SCATTER };
+// How (and whether) a chunk is an all-gather: MakeQuantPlan's last argument.
+enum class QuantGather : uint8_t { NONE, ASSIGN, ACCUMULATE };
 
 struct QuantPlan {
     size_t block = 0, count = 0;       // wire block elems; elements per segment (= result elems)
     size_t nseg = 1;                   // send segments (N for reduce-scatter, else 1)
+    size_t send_seg = 0;               // wire segment of send segment 0 (`me` for all-gather)
+    bool residual = true;              // the prologue carries an error-feedback residual
+    size_t out_segs = 1;               // SCATTER: output segments, seg_bytes apart in recv
+    bool accumulate = false;           // SCATTER: recv += dequantized, not recv =
     size_t seg_bytes = 0, seg_wire = 0;   // strides in send buffer/residual, and in the wire
     size_t scratch_off = 0, err_off = 0, bytes = 0;   // the wire region is at 0
     QuantFinish finish = QuantFinish::DEQUANT;
@@ -48,8 +66,10 @@ struct QuantPlan {
 };
 
 // `sch` is a *Units schedule of rank `me`; `count` elements of `elem_size`
-// bytes per segment. Throws where the schedule does not fit a finish.
+// bytes per segment; `nseg` is the number of wire segments (the send segments
+// of a reduce-scatter, the output segments of an all-gather, which `gather`
+// marks). Throws where the schedule does not fit a finish.
 QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t count,
-                        size_t elem_size);
+                        size_t elem_size, QuantGather gather = QuantGather::NONE);
 
 }  // namespace mlsl

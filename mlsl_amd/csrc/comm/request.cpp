@@ -148,10 +148,17 @@ void CommRequest::SetQuantRsAlgo(QuantRsAlgo a) {
     qrs_algo_ = a;
 }
 
+void CommRequest::SetQuantAccumulate(bool accumulate) {
+    MLSL_CHECK(!setup_done_, "SetQuantAccumulate after Setup");
+    qag_accumulate_ = accumulate;
+}
+
 bool CommRequest::Compressed() const {
-    return comp_ == Compression::QUANT_INT8 &&
-           (spec_.op == CollOp::ALLREDUCE || spec_.op == CollOp::REDUCE_SCATTER) &&
-           (dtype_ == DataType::F32 || dtype_ == DataType::BF16) &&
+    if (comp_ != Compression::QUANT_INT8 ||
+        (dtype_ != DataType::F32 && dtype_ != DataType::BF16))
+        return false;
+    if (spec_.op == CollOp::ALLGATHER) return true;
+    return (spec_.op == CollOp::ALLREDUCE || spec_.op == CollOp::REDUCE_SCATTER) &&
            spec_.rop == ReduceOp::SUM;
 }
 
@@ -202,6 +209,21 @@ void CommRequest::BuildChunks() {
     const int gr = group_->MyIdx(), gs = group_->Size();
     MLSL_CHECK(group_->IsMember(), "request on a group this rank is not in");
     const size_t es = DtypeSize(dtype_);
+    if (comp_ == Compression::QUANT_INT8) {
+        // an all-gather that was asked to be quantized is never run exact
+        // behind the caller's back
+        MLSL_CHECK(spec_.op != CollOp::ALLGATHERV,
+                   "quantized all_gatherv is not supported (equal counts only: use "
+                   "all_gather)");
+        if (spec_.op == CollOp::ALLGATHER) {
+            MLSL_CHECK(dtype_ == DataType::F32 || dtype_ == DataType::BF16,
+                       "quantized all_gather supports f32/bf16 only");
+            MLSL_CHECK(plugin_ == nullptr,
+                       "quantized all_gather cannot run with a compression plugin (the "
+                       "plugin ABI's quant takes a residual and has no accumulate); "
+                       "unset lib_path");
+        }
+    }
 
     // Chunk fan-out. Element-splittable ops slice the message; the ring/
     // pairwise ops (RS, AG(v), AlltoAll(v)) use dedicated chunked builders
@@ -340,7 +362,16 @@ void CommRequest::BuildChunks() {
                 }
                 break;
             case CollOp::ALLGATHER:
-                if (n_chunks > 1) {
+                if (Compressed()) {
+                    // Quantized all-gather: the contribution is quantized once
+                    // into this rank's segment of an N-segment wire, the
+                    // segments travel pairwise and are never requantized, and
+                    // the segmented dequantize finishes all N, the own one
+                    // included. Single chunk, no residual.
+                    const size_t blk = qparams_.block_elems;
+                    ce.sch = BuildAllGatherUnits(gr, gs, (spec_.count + blk - 1) / blk,
+                                                 qparams_.WireBlockBytes(), blk);
+                } else if (n_chunks > 1) {
                     ce.elem_off = 0;
                     std::vector<size_t> counts(static_cast<size_t>(gs), spec_.count);
                     ce.sch = BuildAllGathervChunk(gr, gs, counts, c, n_chunks, dtype_);
@@ -394,10 +425,14 @@ void CommRequest::BuildChunks() {
                 ce.sch = BuildSendRecvList(gr, gs, spec_.pairs, dtype_);
                 break;
         }
-        if (Compressed())
+        if (Compressed()) {
+            const QuantGather gather = spec_.op != CollOp::ALLGATHER ? QuantGather::NONE
+                                       : qag_accumulate_             ? QuantGather::ACCUMULATE
+                                                                     : QuantGather::ASSIGN;
             ce.qplan = MakeQuantPlan(
-                ce.sch, spec_.op == CollOp::REDUCE_SCATTER ? static_cast<size_t>(gs) : 1,
-                static_cast<size_t>(gr), spec_.count, es);
+                ce.sch, spec_.op == CollOp::ALLREDUCE ? 1 : static_cast<size_t>(gs),
+                static_cast<size_t>(gr), spec_.count, es, gather);
+        }
         total_tmp_bytes_ += ce.sch.tmp_bytes;
         // Phase byte 0xFF is reserved for edge-sequenced p2p tags (PairTag);
         // a schedule reaching phase 255 (ring allreduce at 129+ ranks,
@@ -567,22 +602,24 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
             return nullptr;
         };
         if (compressed && !ce.prologue_done) {
-            // quantize user send (+ residual) into the wire
+            // quantize user send (+ residual, where the plan has one) into
+            // the wire
             for (size_t j = 0; j < qp.nseg; ++j) {
                 const uint8_t* seg = sbase + j * qp.seg_bytes;
-                uint8_t* seg_err = wire + qp.err_off + j * qp.seg_bytes;
+                uint8_t* seg_err =
+                    qp.residual ? wire + qp.err_off + j * qp.seg_bytes : nullptr;
+                uint8_t* seg_wire = wire + (qp.send_seg + j) * qp.seg_wire;
                 if (plugin_) {
                     // reference ABI: dtype enum {INT8=0,F16=1,F32=2,F64=3},
                     // comp_ratio = input-elem-bytes (int8 wire), method DFP=1
                     const int sdt = dtype_ == DataType::F32 ? 2
                                     : dtype_ == DataType::F64 ? 3 : 1;
-                    int rc = plugin_->quant(const_cast<uint8_t*>(seg),
-                                            wire + j * qp.seg_wire, qp.count,
+                    int rc = plugin_->quant(const_cast<uint8_t*>(seg), seg_wire, qp.count,
                                             seg_err, sdt, DtypeSize(dtype_), 1);
                     MLSL_CHECK(rc == 0, "quant plugin compress failed");
                 } else {
-                    HostQuantize(seg, seg_err, wire + j * qp.seg_wire, qp.count, qp.block,
-                                 dtype_, true);
+                    HostQuantize(seg, seg_err, seg_wire, qp.count, qp.block, dtype_,
+                                 qp.residual);
                 }
             }
             ce.prologue_done = true;
@@ -678,6 +715,10 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                                 break;
                             case QuantFinish::DEQUANT:
                                 HostDequantize(wires[0], rbase, qp.count, qp.block, dtype_);
+                                break;
+                            case QuantFinish::SCATTER:
+                                HostDequantizeSegments(wires[0], qp.out_segs, rbase, qp.count,
+                                                       qp.block, dtype_, qp.accumulate);
                                 break;
                         }
                     }

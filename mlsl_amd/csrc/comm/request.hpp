@@ -108,8 +108,8 @@ class CommRequest {
     void AddSendRecvList(const std::vector<SRPair>& pairs);
     // Gradient compression (reference quant/quant.c contract): int8 block
     // quantization with error feedback, fused into the collective. Call
-    // before Setup(); honored for ALLREDUCE and REDUCE_SCATTER with SUM on
-    // f32/bf16.
+    // before Setup(); honored for ALLREDUCE and REDUCE_SCATTER with SUM, and
+    // for ALLGATHER (no error feedback there), on f32/bf16.
     void SetCompression(Compression c, const QuantParams& qp);
     // Algorithm of a quantized REDUCE_SCATTER (ignored by every other op).
     // Call before Setup(). DIRECT keeps N-1 segment-wires of scratch where
@@ -117,6 +117,13 @@ class CommRequest {
     // kQuantRsDirectMaxRanks ranks or with a compression plugin.
     void SetQuantRsAlgo(QuantRsAlgo a);
     QuantRsAlgo GetQuantRsAlgo() const { return qrs_algo_; }
+    // Finish of a quantized ALLGATHER (ignored by every other op): false
+    // assigns recv = dequantize(wire), true accumulates recv += it with one
+    // fma per element. Call before Setup(). A quantized ALLGATHER carries no
+    // error-feedback residual in either mode, quantizes every contribution
+    // once (no rank limit), and Setup() fails for it with a compression
+    // plugin.
+    void SetQuantAccumulate(bool accumulate);
     Compression GetCompression() const { return comp_; }
     const QuantParams& QParams() const { return qparams_; }
     const struct QuantPluginApi* Plugin() const { return plugin_; }
@@ -181,6 +188,7 @@ class CommRequest {
     QuantParams qparams_;
     const struct QuantPluginApi* plugin_ = nullptr;  // dlopen'd compression
     QuantRsAlgo qrs_algo_ = QuantRsAlgo::RING;
+    bool qag_accumulate_ = false;
 
     std::vector<ChunkExec> chunks_;
     size_t total_tmp_bytes_ = 0;

@@ -371,6 +371,31 @@ Schedule BuildReduceScatterDirectUnits(int rank, int size, size_t units_per_rank
     return sch;
 }
 
+Schedule BuildAllGatherUnits(int rank, int size, size_t units_per_rank, size_t unit_bytes,
+                             size_t quant_block) {
+    const size_t segB = units_per_rank * unit_bytes;
+    Schedule sch;
+    sch.dtype = DataType::U8;
+    sch.rop = ReduceOp::SUM;
+    sch.quant_block = quant_block;
+    sch.wire_bytes = static_cast<size_t>(size) * segB;
+    sch.result = Ref(Space::RECV, 0, sch.wire_bytes);
+    const int N = size, r = rank;
+    // The pairwise order of BuildReduceScatterDirectUnits; here the own
+    // segment goes out N-1 times and every arrival has a slot in the wire.
+    for (int j = 1; j < N; ++j) {
+        const int to = (r + j) % N, from = (r - j + N) % N;
+        Step st;
+        st.phase = j - 1;
+        st.send_peer = to;
+        st.send = Ref(Space::SEND, static_cast<size_t>(r) * segB, segB);
+        st.recv_peer = from;
+        st.recv = Ref(Space::RECV, static_cast<size_t>(from) * segB, segB);
+        sch.AddStep(st);
+    }
+    return sch;
+}
+
 // Chunked reduce-scatter: the chunk covers output elements [off, off+cnt)
 // of every rank's recv_count-long segment; SEND reads use the FULL-buffer
 // row stride (total*es per rank-row) so independent chunks cover the whole

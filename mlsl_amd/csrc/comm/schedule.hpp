@@ -119,6 +119,17 @@ Schedule BuildReduceScatterUnits(int rank, int size, size_t units_per_rank,
 // needs N-1 segment-wires of scratch where the ring needs 2.
 Schedule BuildReduceScatterDirectUnits(int rank, int size, size_t units_per_rank,
                                        size_t unit_bytes, size_t quant_block);
+// All-gather over the same wire units (quantized path): the wire is N
+// segments of units_per_rank units, segment j being rank j's contribution,
+// and SEND and RECV refs both address it. N-1 pairwise exchanges in
+// BuildAlltoAllvChunk's order: exchange j (phase j-1) sends segment `rank` to
+// (rank+j)%N and receives segment from = (rank-j+N)%N into its own place. No
+// local ops, no TMP; `result` names the whole wire, which the executor's
+// segmented dequantize then turns into N output segments. Every wire crosses
+// one link and no rank forwards what it has just received, unlike the ring
+// of BuildAllGather. size == 1 has no traffic.
+Schedule BuildAllGatherUnits(int rank, int size, size_t units_per_rank, size_t unit_bytes,
+                             size_t quant_block);
 Schedule BuildAllReduceRHD(int rank, int size, size_t count, DataType dt, ReduceOp op);
 // One-shot exchange + local reduce (latency-optimal on full-mesh xGMI;
 // (N-1)x wire cost — small messages only).

@@ -1246,6 +1246,161 @@ void LaunchUnpack(const void* src, void* dst, const PackBlockDesc& d, DataType d
     LaunchPackOrUnpack<false>(src, dst, d, dt, stream);
 }
 
+// ---------------------------------------------------------------------------
+// Segmented dequantize: the finish of the quantized all-gather. The wire is
+// nseg segment wires one after the other, each NumBlocks(count) blocks on a
+// grid of its own, and segment j goes to out[j * count, (j + 1) * count), in
+// one launch for any nseg: the work index runs over all nseg * nblocks wire
+// blocks, and since the segment wires are contiguous, wire block `idx` sits
+// at idx * (block + 8) whatever its segment.
+//
+// Minimum traffic per element: 1 wire byte (+ 8 per block) in, sizeof(T) out,
+// and with ACC another sizeof(T) in. f32: 5.03 B assign, 9.03 B accumulate;
+// bf16: 3.03 B and 5.03 B (block 256).
+
+namespace {
+
+// out = q * scale, or with ACC out = fma(q, scale, out): one explicit fma in
+// float as QFmaSum does it, rounded once into T.
+template <typename T, bool ACC>
+__device__ __forceinline__ T DequantElem(int q, float scale, T old) {
+    if constexpr (ACC)
+        return Encode<T>(__builtin_fmaf(static_cast<float>(q), scale, Decode(old)));
+    else
+        return Encode<T>(q * scale);
+}
+
+// Generic path: any legal block, partial last blocks, any alignment.
+template <typename T, bool ACC>
+__global__ void DequantizeSegmentsKernel(const uint8_t* __restrict__ wire, T* out,
+                                         size_t count, size_t block_elems,
+                                         uint32_t nblocks, FastDiv by_nblocks,
+                                         uint32_t total) {
+    ForEachWaveBlock(total, [&](size_t vidx, int lane) {
+        // uniform across the wave: segment, block and both addresses stay in
+        // scalar registers (as in QuantSumDequantNKernel)
+        const uint32_t idx = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vidx));
+        const uint32_t seg = FDiv(idx, by_nblocks);
+        const uint32_t blk = idx - seg * nblocks;
+        const size_t base = static_cast<size_t>(blk) * block_elems;
+        const size_t n = min(block_elems, count - base);
+        const uint8_t* wblock = wire + static_cast<size_t>(idx) * (block_elems + kWireHdr);
+        const float scale = WireScale(wblock);
+        const int8_t* payload = reinterpret_cast<const int8_t*>(wblock + kWireHdr);
+        // Segment j starts j * count elements in: with a count that is no
+        // multiple of 16 bytes an aligned `out` has misaligned segments, so
+        // the vector width is decided per segment.
+        T* o = out + static_cast<size_t>(seg) * count + base;
+        const bool vec4 = (block_elems & 3) == 0 &&
+                          (reinterpret_cast<uintptr_t>(o - base) & 15) == 0;
+        ForEachBlockElem(n, vec4, lane, [&](size_t i, auto w) {
+            constexpr int W = decltype(w)::value;
+            const int32_t packed = QLoad<W>(payload, i);
+            if constexpr (W == 4) {
+                using V = std::conditional_t<sizeof(T) == 4, float4_ev, ushort4_t>;
+                V v{};
+                if constexpr (ACC) v = *reinterpret_cast<const V*>(o + i);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    v[j] = DequantElem<T, ACC>(QUnpack(packed, j), scale, v[j]);
+                StoreVec<false>(v, o + i);
+            } else {
+                o[i] = DequantElem<T, ACC>(QUnpack(packed, 0), scale, ACC ? o[i] : T{});
+            }
+        });
+    });
+}
+
+// Fast path (block_elems == 256, whole blocks, 16-B aligned `out`): every
+// segment is whole blocks, so wire and output are both flat runs of `nblocks`
+// blocks in all. Two blocks per wave; f32 in the split-half layout of
+// DequantizeF32x2Kernel (each 16-B access contiguous across the half-wave),
+// bf16 eight consecutive elements per lane; with ACC the loads of `out`
+// follow the stores' layout. The wire is only 8-B aligned.
+template <typename T, bool ACC, bool NT_ST>
+__global__ void DequantizeSegmentsX2Kernel(const uint8_t* __restrict__ wire, T* out,
+                                           size_t nblocks) {
+    ForEachHalfWaveBlock(nblocks, [&](size_t blk, int sub) {
+        const uint8_t* wblock = wire + blk * (kFastBlock + kWireHdr);
+        const float scale = WireScale(wblock);
+        T* obase = out + blk * kFastBlock;
+        if constexpr (sizeof(T) == 4) {
+            const int32_t* p4 = reinterpret_cast<const int32_t*>(wblock + kWireHdr);
+            const int32_t pk0 = p4[sub], pk1 = p4[32 + sub];
+            float4_ev o0{}, o1{};
+            if constexpr (ACC) {
+                o0 = *reinterpret_cast<const float4_ev*>(obase + sub * 4);
+                o1 = *reinterpret_cast<const float4_ev*>(obase + 128 + sub * 4);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o0[j] = DequantElem<T, ACC>(QUnpack(pk0, j), scale, o0[j]);
+                o1[j] = DequantElem<T, ACC>(QUnpack(pk1, j), scale, o1[j]);
+            }
+            StoreVec<NT_ST>(o0, obase + sub * 4);
+            StoreVec<NT_ST>(o1, obase + 128 + sub * 4);
+        } else {
+            const uint2_ev packed =
+                *reinterpret_cast<const uint2_ev*>(wblock + kWireHdr + sub * 8);
+            ushort8_t v{};
+            if constexpr (ACC) v = *reinterpret_cast<const ushort8_t*>(obase + sub * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                v[j] = DequantElem<T, ACC>(QUnpack(packed[j >> 2], j & 3), scale, v[j]);
+            StoreVec<NT_ST>(v, obase + sub * 8);
+        }
+    });
+}
+
+template <typename T>
+void DequantizeSegmentsTyped(const uint8_t* wire, size_t nseg, void* out, size_t count,
+                             size_t block_elems, bool accumulate, hipStream_t stream) {
+    const size_t nblocks = NumBlocks(count, block_elems);
+    const size_t total = nseg * nblocks;
+    T* o = static_cast<T*>(out);
+    const bool x2 = block_elems == kFastBlock && count % kFastBlock == 0 &&
+                    (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(wire) & 7) == 0;
+    // Assign mode on the fast path could go to LaunchDequantize's flat kernels
+    // (same bits). Measured at 64 Mi elements, 2 to 8 segments: this kernel
+    // 68 us against 87 us for f32, 49 us against 49 us for bf16
+    // (docs/BENCHMARKS.md), so it keeps both modes.
+    DispatchBool(accumulate, [&](auto acc) {
+        constexpr bool ACC = decltype(acc)::value;
+        if (x2) {
+            // nontemporal stores under LaunchQuantSumDequant's rule
+            DispatchBool(nseg * count * sizeof(T) >= kSumDequantNtBytes, [&](auto nt) {
+                DequantizeSegmentsX2Kernel<T, ACC, decltype(nt)::value>
+                    <<<PairGrid(total), dim3(kBlock), 0, stream>>>(wire, o, total);
+            });
+        } else {
+            MLSL_CHECK(total <= 0xffffffffull, "segmented dequantize: too many wire blocks");
+            DequantizeSegmentsKernel<T, ACC><<<WaveGrid(total), dim3(kBlock), 0, stream>>>(
+                wire, o, count, block_elems, static_cast<uint32_t>(nblocks),
+                MakeFastDiv(static_cast<uint32_t>(nblocks)), static_cast<uint32_t>(total));
+        }
+    });
+}
+
+}  // namespace
+
+void LaunchDequantizeSegments(const void* wire, size_t nseg, void* out, size_t count,
+                              size_t block_elems, DataType dt, bool accumulate,
+                              hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchDequantizeSegments");
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW("segmented dequantize supports f32/bf16 only");
+    MLSL_CHECK(nseg >= 1, "segmented dequantize takes at least one segment");
+    if (count == 0) return;
+    const uint8_t* w = static_cast<const uint8_t*>(wire);
+    if (dt == DataType::F32)
+        DequantizeSegmentsTyped<float>(w, nseg, out, count, block_elems, accumulate, stream);
+    else
+        DequantizeSegmentsTyped<unsigned short>(w, nseg, out, count, block_elems, accumulate,
+                                                stream);
+    HIP_CHECK(hipGetLastError());
+}
+
 // --- IPC p2p transport (comm/p2p_transport.cpp) ---
 // Mailboxes are monotonically increasing u64 sequence counters in the
 // receiver's HBM window; the writer is a remote process on the same or a

@@ -68,6 +68,23 @@ void LaunchQuantSumDequantNT(const void* a_wire, const void* b_wire, void* out,
 // nothing past out[count) is.
 void LaunchQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
                             size_t block_elems, DataType dt, hipStream_t stream);
+// Finish of the quantized all-gather, one launch for any nseg >= 1: `wire`
+// holds nseg segment wires of NumBlocks(count) blocks each, one after the
+// other and every one on a block grid of its own (a partial last block is
+// followed by the next segment's block 0); segment j goes to
+// out[j * count, (j + 1) * count). Assigned with the bits of LaunchDequantize,
+// or with `accumulate` as out = fma(q, scale, out) in float, rounded once
+// into the element type (fp32/bf16). Vector stores are decided per segment,
+// so `out` and count may have any alignment. The wire is not written and
+// nothing past out[nseg * count) is. Outputs of 128 MiB and more are stored
+// nontemporally on the fast path (LaunchQuantSumDequant's rule).
+// Whole 256-blocks in assign mode are contiguous whole blocks, which
+// LaunchDequantize's flat kernels decode to the same bits; this launcher
+// keeps its own kernel there: at 64 Mi elements it took 0.78 of the flat f32
+// kernel's time and the same time as the bf16 one (docs/BENCHMARKS.md).
+void LaunchDequantizeSegments(const void* wire, size_t nseg, void* out, size_t count,
+                              size_t block_elems, DataType dt, bool accumulate,
+                              hipStream_t stream);
 
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,

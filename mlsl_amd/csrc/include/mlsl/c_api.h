@@ -128,6 +128,20 @@ int mlsl_persistent_reduce_scatter_quantized_algo(mlsl_distribution d, size_t re
                                                   mlsl_request* out);
 int mlsl_persistent_all_gather(mlsl_distribution d, size_t send_count, mlsl_data_type dt,
                                mlsl_group g, mlsl_request* out);
+/* int8-quantized all-gather (block size from mlsl_set_quant_params). Every
+ * rank's send_count elements are quantized once, on a block grid of their
+ * own, travel pairwise to every rank and are never requantized. accumulate
+ * == 0: recv[r*send_count + i] = dequantize(wire_r)[i]; accumulate != 0:
+ * recv[r*send_count + i] = fma(q_r[i], scale_r, recv[...]) in float, rounded
+ * once into dt. The rank's own segment takes the same path from its own
+ * wire, so recv is bit-identical on all ranks afterwards (given identical
+ * recv on entry when accumulating). No error feedback: nothing is carried
+ * from one start to the next. send and recv may alias anywhere. No rank
+ * limit. Fails (see mlsl_last_error) unless dt is f32 or bf16, and with a
+ * compression plugin (lib_path); it never runs an exact all-gather instead. */
+int mlsl_persistent_all_gather_quantized(mlsl_distribution d, size_t send_count,
+                                         mlsl_data_type dt, mlsl_group g, int accumulate,
+                                         mlsl_request* out);
 int mlsl_persistent_all_to_all(mlsl_distribution d, size_t send_count, mlsl_data_type dt,
                                mlsl_group g, mlsl_request* out);
 int mlsl_request_start(mlsl_request req, const void* sbuf, void* rbuf);

@@ -43,6 +43,11 @@ def _lib():
                                                    c.c_void_p, c.c_size_t, c.c_size_t,
                                                    c.c_int]
         L.mlsl_host_quant_sum_dequant_n.argtypes = L.mlsl_hip_quant_sum_dequant_n.argtypes
+        L.mlsl_hip_dequantize_segments.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p,
+                                                   c.c_size_t, c.c_size_t, c.c_int, c.c_int]
+        L.mlsl_host_dequantize_segments.argtypes = L.mlsl_hip_dequantize_segments.argtypes
+        L.mlsl_hip_dequantize_segments.restype = c.c_int
+        L.mlsl_host_dequantize_segments.restype = c.c_int
         L.mlsl_host_quantize.argtypes = L.mlsl_hip_quantize.argtypes
         L.mlsl_host_dequantize.argtypes = L.mlsl_hip_dequantize.argtypes
         L.mlsl_host_quant_accum.argtypes = L.mlsl_hip_quant_accum.argtypes
@@ -181,6 +186,20 @@ def quant_sum_dequant_n(wires, out, count, block=256, dtype=None):
                                               DTYPE[dt]))
 
 
+def dequantize_segments(wire, out, count, nseg, block=256, dtype=None, accumulate=False):
+    """The finish of the quantized all_gather in one launch: `wire` holds
+    `nseg` segment wires of wire_bytes(count, block) bytes, each on a block
+    grid of its own, and segment j goes to out[j*count:(j+1)*count] (f32/bf16).
+    Assigned with the bits of `dequantize`, or with accumulate=True as
+    out = fma(q, scale, out) in float, rounded once. Any nseg >= 1; the wire
+    is not written."""
+    wp, _ = _as_ptr_dtype(wire)
+    op_, d1 = _as_ptr_dtype(out)
+    dt = dtype or d1
+    check(_lib().mlsl_hip_dequantize_segments(wp, nseg, op_, count, block, DTYPE[dt],
+                                              1 if accumulate else 0))
+
+
 _ELEM_BYTES = {"f32": 4, "bf16": 2}
 
 
@@ -244,6 +263,16 @@ def host_quant_sum_dequant_n(wires, out, count, block=256, dtype="f32"):
     op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
     check(_lib().mlsl_host_quant_sum_dequant_n(ptrs, len(wires), op_, count, block,
                                                DTYPE[dtype]))
+
+
+def host_dequantize_segments(wire, out, count, nseg, block=256, dtype="f32",
+                             accumulate=False):
+    """Host twin of `dequantize_segments` on numpy arrays: the same bits."""
+    _check_block(block)
+    wp = _host_buf(wire, nseg * wire_bytes(count, block), "wire")
+    op_ = _host_buf(out, nseg * count * _ELEM_BYTES[dtype], "out")
+    check(_lib().mlsl_host_dequantize_segments(wp, nseg, op_, count, block, DTYPE[dtype],
+                                               1 if accumulate else 0))
 
 
 def pack(src, dst, *, mb_offset, mb_count, fm_offset, fm_count, fm_size,

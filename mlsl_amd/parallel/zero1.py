@@ -28,7 +28,8 @@ reduce_scatter(grad) + sharded step + all_gather(param), one exchange of
 each flat buffer per step (the reference's grad RS + increment AG pair).
 With ``compression="int8"`` that reduce_scatter travels as int8 wire blocks
 with error feedback (one persistent request, so the residual carries over
-from step to step); the parameter all_gather stays exact.
+from step to step). The parameter all_gather is exact unless
+``ag_compression="int8"`` is given: see the class.
 """
 import torch
 
@@ -41,9 +42,35 @@ def _dt(t):
 
 
 class ShardedOptimizer:
+    """``ag_compression="int8"`` sends the updated shard back as int8 too.
+
+    Sending int8 *parameters* would cap every weight at 8 bits, so the
+    difference between the owner's exact shard and the replica travels
+    instead, and is accumulated:
+
+    - The owner keeps ``master``, a clone of its shard in the parameter dtype;
+      the wrapped optimizer's parameter and its state live on ``master``.
+      ``flat`` and the model's views are the replica on every rank, the owner
+      included.
+    - After ``opt.step()``, ``delta = master - flat[own]`` goes through one
+      persistent ``all_gather(quantized=True, accumulate=True)`` with
+      ``recv=flat``. Every rank applies the same fma to every segment, its own
+      included, so the replicas stay bit-identical across ranks.
+    - What a step's quantization drops (at most half a step of the block,
+      ``max|delta| / 254``, per element) is still in ``master - replica`` at
+      the next step: the scheme corrects itself, which is why the request
+      carries no residual of its own.
+
+    It needs f32 or bf16 parameters, is independent of ``reduce``,
+    ``compression`` and ``rs_algo``, and costs one extra shard (``master``)
+    and one delta shard per rank. A group of one exchanges nothing and steps
+    on ``flat`` as without it. A model checkpoint holds replica values; a
+    newly constructed optimizer seeds ``master`` from them.
+    """
+
     def __init__(self, params, opt_cls, dist=None, group="data",
                  reduce="none", average=True, compression="none", rs_algo=None,
-                 **opt_kwargs):
+                 ag_compression="none", **opt_kwargs):
         """reduce: "none" (grads already reduced, e.g. by DistributedData)
         or "rs" (this wrapper reduce-scatters raw local grads itself).
         compression: "none", or "int8" for the quantized reduce_scatter
@@ -52,7 +79,10 @@ class ShardedOptimizer:
         rs_algo: algorithm of that quantized reduce_scatter: None
         (MLSL_QUANT_RS_ALGO, ring unless set), "ring", or "direct" (each shard
         goes straight to its owner and is summed once, nothing requantized;
-        at most 8 ranks, N-1 shard-wires of scratch instead of 2)."""
+        at most 8 ranks, N-1 shard-wires of scratch instead of 2).
+        ag_compression: "none" (exact parameter all_gather), or "int8": the
+        quantized, accumulating all_gather of master - replica described in
+        the class docstring (f32 or bf16 parameters)."""
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
@@ -74,6 +104,9 @@ class ShardedOptimizer:
             raise ValueError('rs_algo= selects the quantized reduce_scatter\'s '
                              'algorithm: it needs compression="int8"')
         self.rs_algo = rs_algo
+        if ag_compression not in ("none", "int8"):
+            raise ValueError(f"ag_compression={ag_compression!r}: expected 'none' or 'int8'")
+        self.ag_compression = ag_compression
 
         if torch.cuda.is_available() and self.params[0].is_cuda:
             mx.set_compute_stream(torch.cuda.current_stream().cuda_stream)
@@ -83,6 +116,8 @@ class ShardedOptimizer:
             "one flat group: uniform dtype required"
         if compression == "int8" and dt not in (torch.float32, torch.bfloat16):
             raise ValueError(f'compression="int8" supports f32/bf16 parameters, not {dt}')
+        if ag_compression == "int8" and dt not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'ag_compression="int8" supports f32/bf16 parameters, not {dt}')
         total = sum(p.numel() for p in self.params)
         # pad so the shard divides evenly (owned = ceil math in the
         # reference, mlsl_impl.cpp:401-411; padding is the flat analog)
@@ -100,8 +135,18 @@ class ShardedOptimizer:
         lo = self.rank * self.shard
         self.own_param = self.flat[lo:lo + self.shard]
         self.own_grad = self.flat_grad[lo:lo + self.shard]
+        # int8 all_gather: the optimizer steps on an exact copy of the shard
+        # and flat is the replica everywhere; built once, like _qrs
+        self.master = self._delta = self._qag = None
+        if ag_compression == "int8" and self.world > 1:
+            self.master = self.own_param.detach().clone()
+            self._delta = torch.zeros_like(self.master)
+            self._qag = mx.PersistentRequest(self.dist, "all_gather", self.shard,
+                                             dtype=_dt(self.flat), group=group,
+                                             quantized=True, accumulate=True)
         # the wrapped optimizer sees ONLY the owned shard (state: 1/dp)
-        shard_param = torch.nn.Parameter(self.own_param, requires_grad=False)
+        shard_param = torch.nn.Parameter(
+            self.own_param if self.master is None else self.master, requires_grad=False)
         self._shard_holder = shard_param
         self.opt = opt_cls([shard_param], **opt_kwargs)
         # built once: the request owns the error-feedback residual
@@ -151,7 +196,13 @@ class ShardedOptimizer:
         self.opt.step()
         self._shard_holder.grad = None
 
-        if self.world > 1:
+        if self._qag is not None:
+            # what the replica lacks, last step's rounding included, as int8;
+            # every rank adds every segment the same way
+            torch.sub(self.master, self.own_param, out=self._delta)
+            self._qag.start(self._delta, self.flat)
+            self._qag.wait()
+        elif self.world > 1:
             # increment AllGather (reference StartIncrementComm):
             # every rank's updated shard -> full parameter buffer
             mx.wait(self.dist.all_gather(self.own_param, self.shard,
