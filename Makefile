@@ -147,6 +147,20 @@ $(ASAN_QAG): mlsl_amd/csrc/tests/quant_ag_selftest.cpp mlsl_amd/csrc/comm/schedu
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -ldl -o $@
 
+# The two-shot quantized allreduce under ASan/UBSan: its schedule (slots,
+# routing, the gather, the one SUMQ step), the plan's SUMQ wire table, and the
+# host codec walked through both exchanges by hand inside plan-sized buffers.
+# Pure host C++, like the targets above.
+ASAN_QAR_TWOSHOT := $(BUILD)/quant_ar_twoshot_selftest_asan
+
+asan-quant-ar-twoshot: $(ASAN_QAR_TWOSHOT)
+	$(ASAN_QAR_TWOSHOT)
+
+$(ASAN_QAR_TWOSHOT): mlsl_amd/csrc/tests/quant_ar_twoshot_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/comm/quant_plan.cpp mlsl_amd/csrc/core/log.cpp
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $^ -pthread -ldl -o $@
+
 # What a compressed all-gather request refuses at Setup(), through the C++
 # classes and the library as built (no sanitizer; world 1 over TCP).
 QAG_REQUEST := $(BUILD)/quant_ag_request_selftest

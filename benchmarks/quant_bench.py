@@ -11,6 +11,12 @@ block 256, f32 and bf16; interleaved rounds in one process).
 fan-in at N = 4 and 8 wires: the fused quant_sum_dequant_n kernel against the
 chain of kernels the ring runs on one segment, N-2 quant_accum plus one
 quant_sum_dequant (--melems elements, block 256, f32 and bf16).
+--mode allreduce (the default): quantized (ring, and two-shot up to 8 ranks)
+against exact allreduce of --mbytes MiB, or of --kbytes KiB when given.
+--mode sum_requant_n: single-GPU timing of the two-shot allreduce's
+quant_sum_requant_n kernel at 2, 4 and 8 wires, out of place and in place,
+against its analytic traffic of nwires * (block + 8) bytes read and block + 8
+written per unit (--melems Mi elements, block 256).
 --mode reduce_scatter: quantized (ring, and direct up to 8 ranks) against
 exact reduce-scatter of --melems elements per rank (launch with
 benchmarks/mp_run.py for N>1).
@@ -173,6 +179,66 @@ def sum_dequant_n_ab(args):
                                               _median(times["chain"]), 3)
             print(json.dumps(res), flush=True)
             del out
+
+
+def sum_requant_n(args):
+    """One line of JSON per wire count. Timing as in sum_dequant_ab: host
+    clock around `iters` launch+sync pairs, interleaved rounds;
+    `call_overhead` is the same loop on one unit. In place the destination is
+    the last wire, as the schedule uses it; it is requantized again and again,
+    which changes values and not the bytes moved."""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("sum_requant_n measures GPU kernels: no GPU found")
+    from mlsl_amd import ops
+    torch.cuda.set_device(0)
+    count, block = args.melems << 20, 256
+    units, wbytes = count // block, ops.wire_bytes(count, block)
+    torch.manual_seed(0)
+    wires = []
+    for k in range(8):
+        v = torch.randn(count, dtype=torch.float32, device="cuda") * (1.0 + k)
+        wire = torch.empty(wbytes, dtype=torch.uint8, device="cuda")
+        ops.quantize(v, wire, count, block=block, dtype="f32")
+        wires.append(wire)
+        del v
+    dst = torch.empty(wbytes, dtype=torch.uint8, device="cuda")
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters
+
+    for n in (2, 4, 8):
+        own = wires[n - 1].clone()
+        inplace = wires[:n - 1] + [own]
+        variants = {
+            "out_of_place": lambda: ops.quant_sum_requant_n(wires[:n], dst, units,
+                                                            block=block),
+            "in_place": lambda: ops.quant_sum_requant_n(inplace, own, units, block=block),
+            "call_overhead": lambda: ops.quant_sum_requant_n(wires[:n], dst, 1, block=block),
+        }
+        for fn in variants.values():
+            for _ in range(args.warmup):
+                fn()
+        times = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, fn in variants.items():
+                times[k].append(timed(fn))
+        res = {"config": "quant-sum-requant-n", "nwires": n, "melems": args.melems,
+               "block": block, "iters": args.iters, "rounds": args.rounds}
+        for k, v in times.items():
+            res[f"{k}_us_median"] = round(_median(v) * 1e6, 1)
+            res[f"{k}_us_min"] = round(min(v) * 1e6, 1)
+        traffic = (n + 1) * wbytes   # n wires in, one wire out
+        res["traffic_mib"] = traffic >> 20
+        res["out_of_place_TBps"] = round(traffic / _median(times["out_of_place"]) / 1e12, 3)
+        res["in_place_TBps"] = round(traffic / _median(times["in_place"]) / 1e12, 3)
+        print(json.dumps(res), flush=True)
+        del own
 
 
 def dequant_segments_ab(args):
@@ -340,13 +406,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="allreduce",
                     choices=["allreduce", "reduce_scatter", "all_gather", "sum_dequant_ab",
-                             "sum_dequant_n_ab", "dequant_segments_ab"])
+                             "sum_dequant_n_ab", "dequant_segments_ab", "sum_requant_n"])
     ap.add_argument("--exact-only", action="store_true",
                     help="all_gather mode: time the exact request alone")
     ap.add_argument("--melems", type=int, default=64,
                     help="Mi elements (per rank) for the reduce-scatter and kernel A/B modes")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mbytes", type=int, default=256)
+    ap.add_argument("--kbytes", type=int, default=0,
+                    help="allreduce mode: message size in KiB instead of --mbytes")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -358,6 +426,8 @@ def main():
         return sum_dequant_n_ab(args)
     if args.mode == "dequant_segments_ab":
         return dequant_segments_ab(args)
+    if args.mode == "sum_requant_n":
+        return sum_requant_n(args)
     if args.mode == "all_gather":
         return all_gather_bench(args)
     rs = args.mode == "reduce_scatter"
@@ -378,7 +448,8 @@ def main():
     mx.init()
     rank, size = mx.rank(), mx.world_size()
     es = 2 if args.dtype == "bf16" else 4
-    count = args.mbytes * 1024 * 1024 // es
+    nbytes = args.kbytes * 1024 if args.kbytes else args.mbytes * 1024 * 1024
+    count = nbytes // es
     if rs:
         # `count` stays the send buffer's length; every rank receives 1/size
         count = (args.melems << 20) // size * size
@@ -397,7 +468,7 @@ def main():
                   file=sys.stderr)
             args.dtype = "f32"
             es = 4
-            count = args.mbytes * 1024 * 1024 // es
+            count = nbytes // es
         g = (np.random.randn(count) * 0.01).astype(np.float32)
         out_q = np.empty_like(g)
         out_x = np.empty_like(g)
@@ -408,11 +479,15 @@ def main():
                                 op="sum", group="data", quantized=True)
     xreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype,
                                 op="sum", group="data")
-    # the one-shot quantized reduce-scatter next to the ring (the default)
+    # the one-shot quantized reduce-scatter, or the two-shot quantized
+    # allreduce, next to the ring (the default)
     dreq = None
     if rs and size <= 8:
         dreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype, op="sum",
                                     group="data", quantized=True, algo="direct")
+    elif size <= 8:
+        dreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype, op="sum",
+                                    group="data", quantized=True, ar_algo="two_shot")
     if rs:
         out_q, out_x = out_q[:req_count], out_x[:req_count]
 
@@ -428,7 +503,7 @@ def main():
     todo = [("quantized", qreq, out_q), ("exact", xreq, out_x)]
     if dreq is not None:
         out_d = out_q.clone() if use_cuda else out_q.copy()
-        todo.insert(1, ("quantized_direct", dreq, out_d))
+        todo.insert(1, ("quantized_direct" if rs else "quantized_two_shot", dreq, out_d))
     for name, req, out in todo:
         for _ in range(args.warmup):
             run(req, out)
@@ -443,13 +518,19 @@ def main():
                          "algbw_GBps": round(count * es / dt / 1e9, 2)}
 
     # error of the quantized result vs the exact sum
+    extra = {}
     if use_cuda:
         err = (out_q.float() - out_x.float()).abs().max().item()
         step = out_x.float().abs().max().item() / 127.0
+        if dreq is not None and not rs:
+            extra["two_shot_max_abs_err"] = round(
+                (out_d.float() - out_x.float()).abs().max().item(), 6)
     else:
         import numpy as np
         err = float(np.abs(out_q - out_x).max())
         step = float(np.abs(out_x).max()) / 127.0
+        if dreq is not None and not rs:
+            extra["two_shot_max_abs_err"] = round(float(np.abs(out_d - out_x).max()), 6)
 
     if rank == 0:
         print(json.dumps({
@@ -457,11 +538,13 @@ def main():
                       else "int8-quantized-allreduce",
             "dtype": args.dtype,
             "message_mib": count * es >> 20,
+            "message_bytes": count * es,
             "world": size,
             **{f"{k}_{kk}": vv for k, v in results.items() for kk, vv in v.items()},
             "wire_compression": round(es / ((256 + 8) / 256), 2),
             "max_abs_err": round(err, 6),
             "per_block_step": round(step, 6),
+            **extra,
         }))
     qreq.destroy()
     xreq.destroy()

@@ -14,6 +14,7 @@ DTYPE_SIZE = {"f32": 4, "f64": 8, "u8": 1, "bf16": 2, "f16": 2, "i32": 4, "i64":
 REDOP = {"sum": 0, "min": 1, "max": 2}
 GROUP = {"data": 0, "model": 1, "global": 2}
 QUANT_RS_ALGO = {"ring": 0, "direct": 1}
+QUANT_AR_ALGO = {"ring": 0, "two_shot": 1}
 OPTYPE = {"cc": 0, "bias": 1, "act": 2, "pool": 3, "split": 4, "concat": 5,
           "bcast": 6, "reduce": 7, "data": 8, "eval": 9}
 COMPRESSION = {"none": 0, "int8": 1}
@@ -384,7 +385,7 @@ class PersistentRequest:
     at construction, start/wait/test are allocation-free."""
 
     def __init__(self, dist, kind, count, dtype="f32", op="sum", group="global",
-                 quantized=False, algo=None, accumulate=False):
+                 quantized=False, algo=None, accumulate=False, ar_algo=None):
         """algo: quantized reduce_scatter only. None takes MLSL_QUANT_RS_ALGO
         (ring unless set); "ring" or "direct" names it. See
         mlsl_persistent_reduce_scatter_quantized_algo.
@@ -393,7 +394,10 @@ class PersistentRequest:
         fma per element. Either way every rank, the contributor included,
         decodes the same wire, so recv ends bit-identical across ranks, and
         nothing is carried from one start to the next (no error feedback).
-        See mlsl_persistent_all_gather_quantized."""
+        See mlsl_persistent_all_gather_quantized.
+        ar_algo: quantized all_reduce only. None takes MLSL_QUANT_AR_ALGO
+        (ring unless set); "ring" or "two_shot" names it and overrides the
+        variable. See mlsl_persistent_all_reduce_quantized_algo."""
         import ctypes as _c
         if accumulate and (kind != "all_gather" or not quantized):
             raise ValueError('accumulate=True is the accumulating finish of the '
@@ -408,9 +412,20 @@ class PersistentRequest:
                                  'quantized=True')
             if algo not in QUANT_RS_ALGO:
                 raise ValueError(f"algo={algo!r}: expected None, 'ring' or 'direct'")
+        if ar_algo is not None:
+            if kind != "all_reduce" or not quantized:
+                raise ValueError('ar_algo= selects the quantized all_reduce\'s '
+                                 'algorithm: it needs kind="all_reduce" and '
+                                 'quantized=True')
+            if ar_algo not in QUANT_AR_ALGO:
+                raise ValueError(f"ar_algo={ar_algo!r}: expected None, 'ring' or "
+                                 "'two_shot'")
         L = lib()
         if not hasattr(L, "_persist_declared"):
             P = _c.POINTER
+            L.mlsl_persistent_all_reduce_quantized_algo.argtypes = [
+                c_void_p, c_size_t, c_int, c_int, c_int, c_int, P(c_void_p)]
+            L.mlsl_persistent_all_reduce_quantized_algo.restype = c_int
             L.mlsl_persistent_all_reduce.argtypes = [c_void_p, c_size_t, c_int, c_int,
                                                      c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_reduce_scatter.argtypes = [c_void_p, c_size_t, c_int,
@@ -438,7 +453,17 @@ class PersistentRequest:
                 getattr(L, n).restype = c_int
             L._persist_declared = True
         h = c_void_p()
-        if kind == "all_reduce":
+        if kind == "all_reduce" and ar_algo is not None:
+            # "ring" requantizes a segment on each of its N-1 reduce hops;
+            # "two_shot" sends it to its owner, which sums N wires and
+            # requantizes once (at most 8 ranks, no compression plugin, N-1
+            # range-wires of scratch). Raises for anything but a sum of
+            # f32/bf16 rather than running the exact collective instead.
+            check(L.mlsl_persistent_all_reduce_quantized_algo(
+                dist._h, count, DTYPE[dtype], REDOP[op], GROUP[group],
+                QUANT_AR_ALGO[ar_algo], ctypes.byref(h)))
+        elif kind == "all_reduce":
+            # ar_algo=None: MLSL_QUANT_AR_ALGO decides (ring unless set)
             check(L.mlsl_persistent_all_reduce(dist._h, count, DTYPE[dtype], REDOP[op],
                                                GROUP[group], 1 if quantized else 0,
                                                ctypes.byref(h)))

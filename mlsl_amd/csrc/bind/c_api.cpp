@@ -248,6 +248,28 @@ int mlsl_persistent_all_reduce(mlsl_distribution d, size_t count, mlsl_data_type
     C_CATCH
 }
 
+int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
+                                              mlsl_data_type dt, mlsl_reduction op,
+                                              mlsl_group g, mlsl_quant_ar_algo algo,
+                                              mlsl_request* out) {
+    C_TRY
+    // never fall back to an exact allreduce behind the caller's back
+    MLSL_CHECK(ROP(op) == ReduceOp::SUM,
+               "quantized all_reduce with a named algorithm supports the SUM reduction only");
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized all_reduce with a named algorithm supports f32/bf16 only");
+    MLSL_CHECK(algo == MLSL_QAR_RING || algo == MLSL_QAR_TWO_SHOT,
+               "unknown quantized all_reduce algorithm");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddAllReduce(count, ROP(op));
+    r->SetCompression(Compression::QUANT_INT8,
+                      Environment::GetEnv().GetQuantizationParams());
+    r->SetQuantArAlgo(algo == MLSL_QAR_TWO_SHOT ? QuantArAlgo::TWO_SHOT : QuantArAlgo::RING);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
 int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
                                    mlsl_data_type dt, mlsl_reduction op, mlsl_group g,
                                    mlsl_request* out) {

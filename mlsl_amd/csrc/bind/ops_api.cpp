@@ -138,6 +138,13 @@ int mlsl_hip_quant_sum_dequant_n(const void* const* wires, int nwires, void* out
     OPS_CATCH
 }
 
+int mlsl_hip_quant_sum_requant_n(const void* const* wires, int nwires, void* dst_wire,
+                                 size_t nunits, size_t block) {
+    OPS_TRY LaunchQuantSumRequantN(wires, nwires, dst_wire, nunits, block, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
 int mlsl_hip_dequantize_segments(const void* wire, size_t nseg, void* out, size_t count,
                                  size_t block, int dt, int accumulate) {
     OPS_TRY LaunchDequantizeSegments(wire, nseg, out, count, block,
@@ -178,6 +185,12 @@ int mlsl_host_quant_sum_dequant_n(const void* const* wires, int nwires, void* ou
                                   size_t count, size_t block, int dt) {
     OPS_TRY HostQuantSumDequantN(wires, nwires, out, count, block,
                                  static_cast<DataType>(dt));
+    OPS_CATCH
+}
+
+int mlsl_host_quant_sum_requant_n(const void* const* wires, int nwires, void* dst_wire,
+                                  size_t nunits, size_t block) {
+    OPS_TRY HostQuantSumRequantN(wires, nwires, dst_wire, nunits, block);
     OPS_CATCH
 }
 

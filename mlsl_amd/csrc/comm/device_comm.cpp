@@ -622,6 +622,14 @@ void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t
             uint8_t* src = ptr(st.local_src);
             if (st.local == Step::LocalOp::COPY) {
                 if (d != src) LaunchCopy(d, src, st.local_src.bytes, s);
+            } else if (st.local == Step::LocalOp::SUMQ) {
+                // a compressed chunk's sbase is its plan's base (IssueAll)
+                const QuantPlan& p = ce.qplan;
+                uint8_t* base = const_cast<uint8_t*>(sbase);
+                const void* wires[kQuantRsDirectMaxRanks];
+                for (int k = 0; k < p.sumq_nwires; ++k) wires[k] = base + p.sumq_wire_off[k];
+                LaunchQuantSumRequantN(wires, p.sumq_nwires, base + p.sumq_dst_off,
+                                       p.sumq_units, p.block, s);
             } else if (ce.sch.quant_block > 0) {
                 const size_t blk = ce.sch.quant_block;
                 const size_t units = st.local_dst.bytes / req->QParams().WireBlockBytes();

@@ -496,6 +496,15 @@ void P2pGroup::IssueSchedule(CommRequest* req, ChunkExec& ce, size_t lane,
             uint8_t* src = ptr(st.local_src);
             if (st.local == Step::LocalOp::COPY) {
                 if (d != src) LaunchCopyVariant(d, src, st.local_src.bytes, false, s);
+            } else if (st.local == Step::LocalOp::SUMQ) {
+                // a compressed chunk's sbase is its plan's base; the arrival
+                // slots were filled by this stream's consume kernels above
+                const QuantPlan& p = ce.qplan;
+                uint8_t* base = const_cast<uint8_t*>(sbase);
+                const void* wires[kQuantRsDirectMaxRanks];
+                for (int k = 0; k < p.sumq_nwires; ++k) wires[k] = base + p.sumq_wire_off[k];
+                LaunchQuantSumRequantN(wires, p.sumq_nwires, base + p.sumq_dst_off,
+                                       p.sumq_units, p.block, s);
             } else if (quant) {
                 LaunchQuantAccum(d, src, (st.local_dst.bytes / unit) * blk,
                                  blk, s);

@@ -8,6 +8,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "../core/log.hpp"
 
@@ -30,6 +31,18 @@ inline uint16_t F32B(float f) {
     return static_cast<uint16_t>(u >> 16);
 }
 
+// Wire block: kWireHdr header bytes ([f32 scale][f32 0]) and the payload.
+constexpr size_t kWireHdr = 8;
+// The N-way kernels take their wires by value: at most this many.
+constexpr int kMaxSumWires = 8;
+
+// The requantizing half of the codec, shared by every function that writes a
+// wire block (the device side is QScale / QRound in hip/kernels.hip).
+inline float BlockScale(float block_max) { return block_max > 0.f ? block_max / 127.f : 1.f; }
+inline float QuantRound(float v, float inv_scale) {
+    return std::min(127.f, std::max(-127.f, std::nearbyint(v * inv_scale)));
+}
+
 template <typename LOAD, typename STORE>
 void QuantizeImpl(LOAD load, STORE store, void* wire, size_t count, size_t block,
                   bool use_err) {
@@ -43,14 +56,13 @@ void QuantizeImpl(LOAD load, STORE store, void* wire, size_t count, size_t block
         int8_t* payload = reinterpret_cast<int8_t*>(wb + 8);
         float m = 0.f;
         for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(load(base + i, use_err)));
-        const float scale = m > 0.f ? m / 127.f : 1.f;
+        const float scale = BlockScale(m);
         hdr[0] = scale;
         hdr[1] = 0.f;
         const float inv = 1.f / scale;
         for (size_t i = 0; i < n; ++i) {
             float v = load(base + i, use_err);
-            float q = std::nearbyint(v * inv);
-            q = std::min(127.f, std::max(-127.f, q));
+            const float q = QuantRound(v, inv);
             payload[i] = static_cast<int8_t>(q);
             if (use_err) store(base + i, v - q * scale);
         }
@@ -182,6 +194,44 @@ void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_
             if (dt == DataType::F32) static_cast<float*>(out)[base + i] = acc;
             else static_cast<uint16_t*>(out)[base + i] = F32B(acc);
         }
+    }
+}
+
+void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
+                          size_t nunits, size_t block) {
+    CheckQuantBlock(block, "HostQuantSumRequantN");
+    MLSL_CHECK(nwires >= 1 && nwires <= kMaxSumWires,
+               "quantized sum-requantize takes 1 to 8 wires");
+    MLSL_CHECK(dst_wire != nullptr, "quantized sum-requantize: null destination");
+    for (int r = 0; r < nwires; ++r)
+        MLSL_CHECK(wires[r] != nullptr, "quantized sum-requantize: null wire");
+    // a unit's sums are complete before its first byte is written, so dst_wire
+    // may be one of the wires
+    std::vector<float> acc(block);
+    for (size_t blk = 0; blk < nunits; ++blk) {
+        float s[kMaxSumWires];
+        const int8_t* p[kMaxSumWires];
+        for (int r = 0; r < nwires; ++r) {
+            const uint8_t* wb = static_cast<const uint8_t*>(wires[r]) + blk * (block + kWireHdr);
+            std::memcpy(&s[r], wb, 4);
+            p[r] = reinterpret_cast<const int8_t*>(wb + kWireHdr);
+        }
+        float m = 0.f;
+        for (size_t i = 0; i < block; ++i) {
+            // wire order, one explicit fma per wire: the device kernel's bits
+            float a = 0.f;
+            for (int r = 0; r < nwires; ++r)
+                a = std::fmaf(static_cast<float>(p[r][i]), s[r], a);
+            acc[i] = a;
+            m = std::max(m, std::fabs(a));
+        }
+        const float scale = BlockScale(m);
+        const float inv = 1.f / scale;
+        uint8_t* db = static_cast<uint8_t*>(dst_wire) + blk * (block + kWireHdr);
+        int8_t* dp = reinterpret_cast<int8_t*>(db + kWireHdr);
+        for (size_t i = 0; i < block; ++i) dp[i] = static_cast<int8_t>(QuantRound(acc[i], inv));
+        const float hdr[2] = {scale, 0.f};
+        std::memcpy(db, hdr, kWireHdr);
     }
 }
 

@@ -35,6 +35,14 @@ void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
 // LaunchQuantSumDequantN computes.
 void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
                           size_t block, DataType dt);
+// dst_wire = requantize(sum over r of dequant(wires[r])), 1 to 8 wires, over
+// nunits whole wire units: the owner's step of the two-shot quantized
+// allreduce. The sum is HostQuantSumDequantN's in float; the requantize is
+// HostQuantize's (scale = max / 127 or 1, rint(v * (1 / scale)) clamped,
+// second header word 0). dst_wire may be exactly one of the wires, or overlap
+// none. Bit for bit what LaunchQuantSumRequantN computes.
+void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
+                          size_t nunits, size_t block);
 // The finish of the quantized all-gather: `wire` holds nseg segment wires of
 // QuantWireBytes(count, block) bytes each, every one on a block grid of its
 // own, and segment j goes to out[j * count, (j + 1) * count): assigned as

@@ -53,6 +53,34 @@ QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t coun
     } else {
         p.wire_off[0] = res.off;
     }
+    // Two-shot allreduce: the one SUMQ step's wire table. The arrival slots
+    // are the TMP receives before it, one per peer, of the own range's size.
+    for (const Step& st : sch.steps) {
+        if (st.local != Step::LocalOp::SUMQ) continue;
+        MLSL_CHECK(p.sumq_nwires == 0 && nseg == 1 && sch.fan_in == 0 &&
+                       st.local_src.space == Space::TMP && st.local_dst.space != Space::TMP,
+                   "a SUMQ step belongs to a two-shot allreduce, once");
+        size_t slots = 0;
+        for (const Step& a : sch.steps)
+            if (a.phase < st.phase && a.recv_peer >= 0 && a.recv.space == Space::TMP) {
+                MLSL_CHECK(a.recv.bytes == st.local_dst.bytes,
+                           "two-shot arrival slots have the own range's size");
+                ++slots;
+            }
+        MLSL_CHECK(slots + 1 <= static_cast<size_t>(kQuantRsDirectMaxRanks) && me <= slots &&
+                       slots * st.local_dst.bytes == st.local_src.bytes,
+                   "two-shot requantize takes one wire per rank, 8 at the most");
+        const size_t units = (count + p.block - 1) / p.block;
+        const size_t unit_bytes = units ? sch.wire_bytes / units : 0;
+        p.sumq_nwires = static_cast<int>(slots + 1);
+        p.sumq_dst_off = st.local_dst.off;
+        p.sumq_units = unit_bytes ? st.local_dst.bytes / unit_bytes : 0;
+        for (size_t r = 0; r <= slots; ++r)
+            p.sumq_wire_off[r] =
+                r == me ? st.local_dst.off
+                        : p.scratch_off + st.local_src.off +
+                              (r < me ? r : r - 1) * st.local_dst.bytes;
+    }
     return p;
 }
 

@@ -18,9 +18,15 @@
 // and the residual) into wire segment send_seg + j (seg_wire apart), each on
 // a block grid of its own and with the residual only where `residual` says
 // so, before anything writes the recv buffer: the two may alias anywhere.
-// Then the schedule runs, then the finish writes `count` elements, or
-// out_segs * count for SCATTER:
-//   DEQUANT  allreduce, and any op on a group of one: dequantize wire_off[0]
+// Then the schedule runs. Its local ops are REDUCE (QuantAccum of the step's
+// own two ranges) and, in the two-shot allreduce only, one SUMQ: the
+// sumq_nwires wires at sumq_wire_off[], sumq_units units each, are summed in
+// that order and requantized once into sumq_dst_off, which is one of them
+// (the own range, at position `me`; the others are the arrival slots in TMP).
+// A rank that owns no units has sumq_units == 0 and skips the op.
+// Then the finish writes `count` elements, or out_segs * count for SCATTER:
+//   DEQUANT  allreduce (ring or two-shot: the whole wire at wire_off[0] = 0),
+//            and any op on a group of one: dequantize wire_off[0]
 //   SUM2     ring reduce-scatter: the partial sum that arrived last
 //            (wire_off[0], in TMP) plus this rank's own segment (wire_off[1]),
 //            one fused kernel
@@ -63,6 +69,13 @@ struct QuantPlan {
     QuantFinish finish = QuantFinish::DEQUANT;
     int nwires = 1;                    // 1, 2, or fan_in + 1
     size_t wire_off[kQuantRsDirectMaxRanks] = {};   // in the order the finish sums them
+    // The schedule's SUMQ step (two-shot allreduce); sumq_nwires == 0 where the
+    // schedule has none. Offsets from the chunk base, wires in summing order
+    // (ascending group rank, the own range at position `me`).
+    int sumq_nwires = 0;
+    size_t sumq_wire_off[kQuantRsDirectMaxRanks] = {};
+    size_t sumq_dst_off = 0;           // the own range: one of sumq_wire_off
+    size_t sumq_units = 0;             // wire units per wire; 0: this rank owns nothing
 };
 
 // `sch` is a *Units schedule of rank `me`; `count` elements of `elem_size`

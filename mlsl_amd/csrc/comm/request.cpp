@@ -148,6 +148,12 @@ void CommRequest::SetQuantRsAlgo(QuantRsAlgo a) {
     qrs_algo_ = a;
 }
 
+void CommRequest::SetQuantArAlgo(QuantArAlgo a) {
+    MLSL_CHECK(!setup_done_, "SetQuantArAlgo after Setup");
+    qar_algo_ = a;
+    qar_named_ = true;
+}
+
 void CommRequest::SetQuantAccumulate(bool accumulate) {
     MLSL_CHECK(!setup_done_, "SetQuantAccumulate after Setup");
     qag_accumulate_ = accumulate;
@@ -303,10 +309,29 @@ void CommRequest::BuildChunks() {
                     // compressed-domain accumulation (quant/quant.c path
                     // fused into the collective — reference cqueue.c:1977,
                     // 2283). Single chunk; the wire lives in TMP.
+                    // With TWO_SHOT every wire range goes straight to its
+                    // owner, which sums N wires and requantizes once, and
+                    // the ranges are gathered pairwise (schedule.hpp).
                     const size_t blk = qparams_.block_elems;
                     const size_t nblocks = (cnt + blk - 1) / blk;
-                    ce.sch = BuildAllReduceRingUnits(gr, gs, nblocks,
-                                                     qparams_.WireBlockBytes(), blk);
+                    const QuantArAlgo qar = qar_named_ ? qar_algo_ : cfg.quant_ar_algo;
+                    if (qar == QuantArAlgo::TWO_SHOT) {
+                        const std::string from_env =
+                            qar_named_ ? "" : " (chosen by MLSL_QUANT_AR_ALGO=two_shot)";
+                        MLSL_CHECK(gs <= kQuantRsDirectMaxRanks,
+                                   "two-shot quantized all_reduce supports at most 8 "
+                                   "ranks per group (its requantize takes 8 wires); use "
+                                   "the ring" + from_env);
+                        MLSL_CHECK(plugin_ == nullptr,
+                                   "two-shot quantized all_reduce cannot run with a "
+                                   "compression plugin (the plugin ABI has no N-way "
+                                   "sum); use the ring or unset lib_path" + from_env);
+                        ce.sch = BuildAllReduceTwoShotUnits(gr, gs, nblocks,
+                                                            qparams_.WireBlockBytes(), blk);
+                    } else {
+                        ce.sch = BuildAllReduceRingUnits(gr, gs, nblocks,
+                                                         qparams_.WireBlockBytes(), blk);
+                    }
                 } else if (algo == AllReduceAlgo::DIRECT) {
                     ce.sch = BuildAllReduceDirect(gr, gs, cnt, dtype_, spec_.rop);
                 } else if (algo == AllReduceAlgo::RHD && (gs & (gs - 1)) == 0) {
@@ -664,6 +689,17 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                         uint8_t* s = ptr(st.local_src);
                         if (st.local == Step::LocalOp::COPY) {
                             if (d != s) std::memmove(d, s, st.local_src.bytes);
+                        } else if (st.local == Step::LocalOp::SUMQ) {
+                            // the owner's N wires from the plan, summed and
+                            // requantized once into the own range (refused
+                            // with a plugin at Setup)
+                            const void* in[kQuantRsDirectMaxRanks];
+                            for (int k = 0; k < qp.sumq_nwires; ++k)
+                                in[k] = wire + qp.sumq_wire_off[k];
+                            if (qp.sumq_units > 0)
+                                HostQuantSumRequantN(in, qp.sumq_nwires,
+                                                     wire + qp.sumq_dst_off, qp.sumq_units,
+                                                     qp.block);
                         } else if (ce.sch.quant_block > 0) {
                             const size_t blk = ce.sch.quant_block;
                             const size_t units =

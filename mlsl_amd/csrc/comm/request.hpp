@@ -117,6 +117,12 @@ class CommRequest {
     // kQuantRsDirectMaxRanks ranks or with a compression plugin.
     void SetQuantRsAlgo(QuantRsAlgo a);
     QuantRsAlgo GetQuantRsAlgo() const { return qrs_algo_; }
+    // Algorithm of a quantized ALLREDUCE (ignored by every other op). Call
+    // before Setup(). A request that never calls this takes
+    // MLSL_QUANT_AR_ALGO (ring unless set) at Setup(). TWO_SHOT keeps N-1
+    // range-wires of scratch, and Setup() fails for it on a group of more
+    // than kQuantRsDirectMaxRanks ranks or with a compression plugin.
+    void SetQuantArAlgo(QuantArAlgo a);
     // Finish of a quantized ALLGATHER (ignored by every other op): false
     // assigns recv = dequantize(wire), true accumulates recv += it with one
     // fma per element. Call before Setup(). A quantized ALLGATHER carries no
@@ -189,6 +195,8 @@ class CommRequest {
     const struct QuantPluginApi* plugin_ = nullptr;  // dlopen'd compression
     QuantRsAlgo qrs_algo_ = QuantRsAlgo::RING;
     bool qag_accumulate_ = false;
+    QuantArAlgo qar_algo_ = QuantArAlgo::RING;   // meaningful once qar_named_
+    bool qar_named_ = false;   // false: MLSL_QUANT_AR_ALGO decides at Setup()
 
     std::vector<ChunkExec> chunks_;
     size_t total_tmp_bytes_ = 0;

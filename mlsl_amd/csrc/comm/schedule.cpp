@@ -158,6 +158,56 @@ Schedule BuildAllReduceRingUnits(int rank, int size, size_t units, size_t unit_b
     return sch;
 }
 
+Schedule BuildAllReduceTwoShotUnits(int rank, int size, size_t units, size_t unit_bytes,
+                                    size_t quant_block) {
+    Schedule sch;
+    sch.dtype = DataType::U8;
+    sch.rop = ReduceOp::SUM;
+    sch.quant_block = quant_block;
+    sch.wire_bytes = units * unit_bytes;
+    sch.result = Ref(Space::SEND, 0, sch.wire_bytes);
+    if (size == 1) return sch;
+    const int N = size, r = rank;
+    const size_t parts = static_cast<size_t>(N);
+    auto range = [&](int owner) {
+        return Ref(Space::SEND, SegOffset(units, parts, owner) * unit_bytes,
+                   SegCount(units, parts, owner) * unit_bytes);
+    };
+    const BufRef own = range(r);
+    sch.tmp_bytes = static_cast<size_t>(N - 1) * own.bytes;
+    // Phase A: BuildReduceScatterDirectUnits' exchanges over unit ranges.
+    for (int j = 1; j < N; ++j) {
+        const int to = (r + j) % N, from = (r - j + N) % N;
+        Step st;
+        st.phase = j - 1;
+        st.send_peer = to;
+        st.send = range(to);
+        st.recv_peer = from;
+        st.recv = Ref(Space::TMP, static_cast<size_t>(from < r ? from : from - 1) * own.bytes,
+                      own.bytes);
+        sch.AddStep(st);
+    }
+    // The owner's N wires, summed and requantized once, in place.
+    Step sumq;
+    sumq.phase = N - 1;
+    sumq.local = Step::LocalOp::SUMQ;
+    sumq.local_src = Ref(Space::TMP, 0, sch.tmp_bytes);
+    sumq.local_dst = own;
+    sch.AddStep(sumq);
+    // Phase B: BuildAllGatherUnits' exchanges over the same ranges.
+    for (int j = 1; j < N; ++j) {
+        const int to = (r + j) % N, from = (r - j + N) % N;
+        Step st;
+        st.phase = N - 1 + j;
+        st.send_peer = to;
+        st.send = own;
+        st.recv_peer = from;
+        st.recv = range(from);
+        sch.AddStep(st);
+    }
+    return sch;
+}
+
 // Direct (one-shot) allreduce: every rank sends its whole buffer to every
 // peer in ONE exchange phase and reduces the N-1 arrivals locally. On a
 // fully-connected xGMI node this drives all N-1 point-to-point links
@@ -869,6 +919,12 @@ void SimulateSchedules(const std::vector<Schedule>& per_rank,
         max_phase = std::max(max_phase, s.num_phases);
     }
     for (int r = 0; r < N; ++r) tmp[r].resize(per_rank[r].tmp_bytes);
+    for (const auto& s : per_rank)
+        for (const auto& st : s.steps)
+            MLSL_CHECK(st.local != Step::LocalOp::SUMQ,
+                       "simulator: a SUMQ step (two-shot quantized allreduce) needs "
+                       "the int8 codec and the chunk's plan; it is not a REDUCE and "
+                       "is not simulated here");
 
     auto ptr = [&](int r, const BufRef& b) -> uint8_t* {
         switch (b.space) {

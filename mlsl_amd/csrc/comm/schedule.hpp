@@ -43,7 +43,12 @@ struct Step {
     BufRef send;
     int recv_peer = -1;
     BufRef recv;
-    enum class LocalOp : uint8_t { NONE = 0, REDUCE = 1, COPY = 2 };
+    // SUMQ (two-shot quantized allreduce only): local_src is the whole TMP
+    // range, local_dst this rank's own range of the wire; the N wires of that
+    // range (the TMP slots and local_dst itself at position `rank`, ascending
+    // group rank) are summed and requantized once into local_dst, in place.
+    // The executors take the wire table from the chunk's plan (quant_plan.hpp).
+    enum class LocalOp : uint8_t { NONE = 0, REDUCE = 1, COPY = 2, SUMQ = 3 };
     LocalOp local = LocalOp::NONE;
     BufRef local_src;     // REDUCE: dst += src ; COPY: dst = src
     BufRef local_dst;
@@ -130,6 +135,24 @@ Schedule BuildReduceScatterDirectUnits(int rank, int size, size_t units_per_rank
 // of BuildAllGather. size == 1 has no traffic.
 Schedule BuildAllGatherUnits(int rank, int size, size_t units_per_rank, size_t unit_bytes,
                              size_t quant_block);
+// Two-shot quantized allreduce over the flat wire of `units` units. Rank r
+// owns the unit range [SegOffset(units, N, r), + SegCount(units, N, r)); with
+// units < N some ranks own nothing and their exchanges carry zero bytes.
+//   phases 0..N-2    exchange j (BuildAlltoAllvChunk's order) sends the range
+//                    of to = (rank+j)%N from SEND to its owner and receives
+//                    this rank's range from from = (rank-j+N)%N into TMP slot
+//                    (from < rank ? from : from-1); N-1 slots of the own
+//                    range's size. No local ops.
+//   phase N-1        one step without traffic: LocalOp::SUMQ, local_src the
+//                    whole TMP range, local_dst the own range of the wire.
+//   phases N..2N-2   BuildAllGatherUnits' exchanges over the ranges: send the
+//                    own range, receive from's range into its place.
+// `result` is the whole wire in SEND space, which every rank dequantizes, the
+// owner of a range included: outputs are bit-identical across ranks. Every
+// range is requantized once whatever N is; each rank sends the ring's wire
+// bytes, 2(N-1)/N of the wire. fan_in stays 0. size == 1: no steps, no TMP.
+Schedule BuildAllReduceTwoShotUnits(int rank, int size, size_t units, size_t unit_bytes,
+                                    size_t quant_block);
 Schedule BuildAllReduceRHD(int rank, int size, size_t count, DataType dt, ReduceOp op);
 // One-shot exchange + local reduce (latency-optimal on full-mesh xGMI;
 // (N-1)x wire cost — small messages only).
@@ -173,7 +196,9 @@ Schedule BuildSendRecvList(int rank, int size, const std::vector<SRPair>& pairs,
 // CPU reference executor: runs `size` ranks' schedules against in-memory
 // buffers, delivering messages instantly. Used by unit tests to validate
 // schedule semantics without sockets or GPUs, and by the planner's
-// isolation-statistics dry-run mode.
+// isolation-statistics dry-run mode. A schedule with a SUMQ step is refused:
+// that op needs the int8 codec and the chunk's plan, which live above this
+// file (csrc/tests/quant_ar_twoshot_selftest.cpp walks it through the codec).
 void SimulateSchedules(const std::vector<Schedule>& per_rank,
                        std::vector<std::vector<uint8_t>>& send_bufs,
                        std::vector<std::vector<uint8_t>>& recv_bufs);

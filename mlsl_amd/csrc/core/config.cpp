@@ -52,6 +52,11 @@ Config Config::FromEnv() {
         else if (!std::strcmp(e, "ring") || !*e) c.quant_rs_algo = QuantRsAlgo::RING;
         else MLSL_THROW(std::string("MLSL_QUANT_RS_ALGO=") + e + ": expected ring or direct");
     }
+    if (const char* e = std::getenv("MLSL_QUANT_AR_ALGO")) {
+        if (!std::strcmp(e, "two_shot")) c.quant_ar_algo = QuantArAlgo::TWO_SHOT;
+        else if (!std::strcmp(e, "ring") || !*e) c.quant_ar_algo = QuantArAlgo::RING;
+        else MLSL_THROW(std::string("MLSL_QUANT_AR_ALGO=") + e + ": expected ring or two_shot");
+    }
     c.heap_mb = EnvSize("MLSL_HEAP_SIZE_MB", 0);
     c.check_pointers = EnvBool("MLSL_CHECK_POINTERS", false);
     if (const char* e = std::getenv("MLSL_TRANSPORT")) c.transport = e;

@@ -44,6 +44,9 @@ struct Config {
     // MLSL_QUANT_RS_ALGO=ring|direct: quantized reduce-scatter requests that
     // do not name an algorithm
     QuantRsAlgo quant_rs_algo = QuantRsAlgo::RING;
+    // MLSL_QUANT_AR_ALGO=ring|two_shot: quantized allreduce requests that do
+    // not name an algorithm (ParameterSet gradients under QUANT=1 included)
+    QuantArAlgo quant_ar_algo = QuantArAlgo::RING;
     size_t heap_mb = 0;            // MLSL_HEAP_SIZE_MB: device pool pre-reserve
     bool check_pointers = false;   // MLSL_CHECK_POINTERS: validate collective bufs
     std::string transport = "auto";  // MLSL_TRANSPORT=auto|tcp|rccl

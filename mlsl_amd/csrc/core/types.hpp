@@ -101,7 +101,17 @@ enum class QuantRsAlgo : int {
     DIRECT = 1,
 };
 // DIRECT's fan-in kernel takes the wires by value: at most this many ranks.
+// (The two-shot allreduce's requantize kernel shares the limit.)
 constexpr int kQuantRsDirectMaxRanks = 8;
+
+// How a quantized allreduce moves its wire (MLSL_QUANT_AR_ALGO, or per
+// request). RING requantizes a segment's partial sum on each of the N-1 hops
+// of its reduce half; TWO_SHOT sends every segment straight to its owner,
+// which sums the N wires and requantizes once, then gathers the segments.
+enum class QuantArAlgo : int {
+    RING = 0,
+    TWO_SHOT = 1,
+};
 
 // Block-quantization parameters (reference QuantParams
 // include/mlsl.hpp:162-171). Built-in int8 HIP/CPU kernels by default; a

@@ -854,6 +854,100 @@ __global__ void QuantSumDequantNX2Kernel(QuantWires ws, T* __restrict__ out,
     });
 }
 
+// The owner's step of the two-shot quantized allreduce: dst = requantize(sum
+// of NW dequantized wires), over whole wire units. The sum is QFmaSum, the
+// requantize is QuantizeKernel's (QScale, 1/scale, QRound, QPack,
+// WriteWireHeader). `dst` may be exactly one of the wires, so neither side is
+// __restrict__: a lane stores only payload bytes it has itself loaded, and the
+// header is stored after the cross-lane maximum, which needs every lane's
+// scale loads. Plain stores: the destination is sent to peers next.
+//
+// Generic path: any legal block, one wave per unit, two passes. The second
+// pass recomputes the fma chain instead of holding a block in registers.
+template <int NW>
+__global__ void QuantSumRequantNKernel(QuantWires ws, uint8_t* dst, size_t nunits,
+                                       size_t block_elems) {
+    ForEachWaveBlock(nunits, [&](size_t vblk, int lane) {
+        // scalar block index, as in QuantSumDequantNKernel
+        const size_t blk =
+            (static_cast<size_t>(__builtin_amdgcn_readfirstlane(
+                 static_cast<uint32_t>(vblk >> 32))) << 32) |
+            static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vblk)));
+        const int8_t* payload[NW];
+        float s[NW];
+#pragma unroll
+        for (int r = 0; r < NW; ++r) {
+            const uint8_t* wblock = ws.w[r] + blk * (block_elems + kWireHdr);
+            s[r] = WireScale(wblock);
+            payload[r] = reinterpret_cast<const int8_t*>(wblock + kWireHdr);
+        }
+        uint8_t* dblock = dst + blk * (block_elems + kWireHdr);
+        int8_t* dpayload = reinterpret_cast<int8_t*>(dblock + kWireHdr);
+
+        float m = 0.f;
+        ForEachBlockElem(block_elems, true, lane, [&](size_t i, auto w) {
+            constexpr int W = decltype(w)::value;
+            int32_t p[NW];
+#pragma unroll
+            for (int r = 0; r < NW; ++r) p[r] = QLoad<W>(payload[r], i);
+#pragma unroll
+            for (int j = 0; j < W; ++j) m = fmaxf(m, fabsf(QFmaSum<NW>(p, s, j)));
+        });
+        const float scale = QScale(WaveMax(m));
+        const float inv = 1.f / scale;
+        ForEachBlockElem(block_elems, true, lane, [&](size_t i, auto w) {
+            constexpr int W = decltype(w)::value;
+            int32_t p[NW];
+#pragma unroll
+            for (int r = 0; r < NW; ++r) p[r] = QLoad<W>(payload[r], i);
+            uint32_t packed = 0;
+#pragma unroll
+            for (int j = 0; j < W; ++j) packed |= QPack(QRound(QFmaSum<NW>(p, s, j), inv), j);
+            QStore<W>(dpayload, i, packed);
+        });
+        if (lane == 0) WriteWireHeader(dblock, scale);
+    });
+}
+
+// Fast path (block_elems == 256, 8-B aligned wires and dst): one unit per
+// half-wave, the 8 sums of a lane live in registers across the half-wave
+// maximum, so each wire costs a lane one 8-B payload load and the result one
+// 8-B payload store.
+template <int NW>
+__global__ void QuantSumRequantNX2Kernel(QuantWires ws, uint8_t* dst, size_t nunits) {
+    ForEachHalfWaveBlock(nunits, [&](size_t blk, int sub) {
+        uint2_ev pw[NW];
+        float s[NW];
+#pragma unroll
+        for (int r = 0; r < NW; ++r) {
+            const uint8_t* wblock = ws.w[r] + blk * (kFastBlock + kWireHdr);
+            s[r] = WireScale(wblock);
+            pw[r] = *reinterpret_cast<const uint2_ev*>(wblock + kWireHdr + sub * 8);
+        }
+        float v[8];
+        float m = 0.f;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            int32_t p[NW];
+#pragma unroll
+            for (int r = 0; r < NW; ++r) p[r] = static_cast<int32_t>(pw[r][h]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[4 * h + j] = QFmaSum<NW>(p, s, j);
+                m = fmaxf(m, fabsf(v[4 * h + j]));
+            }
+        }
+        const float scale = QScale(HalfWaveMax(m));
+        const float inv = 1.f / scale;
+        uint2_ev packed{0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) packed[j >> 2] |= QPack(QRound(v[j], inv), j & 3);
+        uint8_t* dblock = dst + blk * (kFastBlock + kWireHdr);
+        StoreVec<false>(packed, dblock + kWireHdr + sub * 8);
+        if (sub == 0) WriteWireHeader(dblock, scale);
+    });
+}
+
 inline size_t NumBlocks(size_t count, size_t block_elems) {
     return (count + block_elems - 1) / block_elems;
 }
@@ -1106,6 +1200,41 @@ void LaunchQuantSumDequantN(const void* const* wires, int nwires, void* out, siz
     else
         QuantSumDequantNTyped<unsigned short>(ws, nwires, x2, out, count, block_elems,
                                               stream);
+    HIP_CHECK(hipGetLastError());
+}
+
+// Aliasing contract: dst_wire may be EXACTLY one of `wires` (the two-shot
+// allreduce requantizes into the owner's own range in place) or overlap none
+// of them; a partial overlap is not supported. The kernels keep it: a lane
+// stores only payload bytes it has loaded itself, and a unit's header is
+// stored after the unit's cross-lane maximum, which needs all its scale loads.
+void LaunchQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
+                            size_t nunits, size_t block_elems, hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchQuantSumRequantN");
+    MLSL_CHECK(nwires >= 1 && nwires <= kMaxSumWires,
+               "quantized sum-requantize takes 1 to 8 wires");
+    MLSL_CHECK(dst_wire != nullptr, "quantized sum-requantize: null destination");
+    QuantWires ws{};
+    // headers are floats and payloads are read as 4-byte words
+    uintptr_t align = reinterpret_cast<uintptr_t>(dst_wire);
+    for (int r = 0; r < nwires; ++r) {
+        MLSL_CHECK(wires[r] != nullptr, "quantized sum-requantize: null wire");
+        ws.w[r] = static_cast<const uint8_t*>(wires[r]);
+        align |= reinterpret_cast<uintptr_t>(wires[r]);
+    }
+    MLSL_CHECK((align & 3) == 0, "quantized sum-requantize: wires must be 4-byte aligned");
+    if (nunits == 0) return;
+    const bool x2 = block_elems == kFastBlock && (align & 7) == 0;
+    uint8_t* dst = static_cast<uint8_t*>(dst_wire);
+    DispatchWires(nwires, [&](auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        if (x2)
+            QuantSumRequantNX2Kernel<NW><<<PairGrid(nunits), dim3(kBlock), 0, stream>>>(
+                ws, dst, nunits);
+        else
+            QuantSumRequantNKernel<NW><<<WaveGrid(nunits), dim3(kBlock), 0, stream>>>(
+                ws, dst, nunits, block_elems);
+    });
     HIP_CHECK(hipGetLastError());
 }
 

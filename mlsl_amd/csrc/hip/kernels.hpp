@@ -68,6 +68,21 @@ void LaunchQuantSumDequantNT(const void* a_wire, const void* b_wire, void* out,
 // nothing past out[count) is.
 void LaunchQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
                             size_t block_elems, DataType dt, hipStream_t stream);
+// The owner's step of the two-shot quantized allreduce: dst_wire = the sum of
+// dequant(wires[r]) over r = 0..nwires-1 (1 to 8 wires), requantized once,
+// over `nunits` whole wire units of block_elems + 8 bytes. No element count
+// and no dtype: the padding of a partial block is zero in every wire, sums to
+// zero and requantizes to zero. Per element acc = +0, then
+// acc = fma(q_r, scale_r, acc) in wire order; the block's scale is
+// max|acc| / 127 (1 for an all-zero block), q = clamp(rint(acc * (1 / scale)));
+// the header's second word is 0. The host twin computes the same bits.
+// Wires must be 4-byte aligned; 8-byte aligned wires of 256-blocks take a
+// register-resident fast path. dst_wire may be EXACTLY one of the wires (the
+// sum then replaces it in place) or overlap none; never partially. Stores
+// are plain: the destination is handed to peers next. `wires` is a host array
+// read during the call.
+void LaunchQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
+                            size_t nunits, size_t block_elems, hipStream_t stream);
 // Finish of the quantized all-gather, one launch for any nseg >= 1: `wire`
 // holds nseg segment wires of NumBlocks(count) blocks each, one after the
 // other and every one on a block grid of its own (a partial last block is

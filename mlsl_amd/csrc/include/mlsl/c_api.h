@@ -99,6 +99,25 @@ int mlsl_distribution_send_recv_list(mlsl_distribution d, const void* sbuf, void
 int mlsl_persistent_all_reduce(mlsl_distribution d, size_t count, mlsl_data_type dt,
                                mlsl_reduction op, mlsl_group g, int quantized,
                                mlsl_request* out);
+/* The int8-quantized allreduce (quantized != 0 above) with its algorithm
+ * named; the function above takes MLSL_QUANT_AR_ALGO=ring|two_shot, default
+ * ring.
+ * MLSL_QAR_RING: a ring over wire blocks; each of the N-1 hops of the reduce
+ * half requantizes the partial sum, so the error grows with the group.
+ * MLSL_QAR_TWO_SHOT: every wire range goes straight to its owner, which sums
+ * the N wires in fp32 and requantizes once; the owners' ranges are then
+ * gathered pairwise and every rank, the owner included, dequantizes the same
+ * wire, so results are bit-identical across ranks. The wire bytes sent per
+ * rank are the ring's. Scratch: N-1 range-wires. The requantization error is
+ * not carried in the residual (neither is the ring's). Fails at creation on a
+ * group of more than 8 ranks or with a compression plugin (lib_path).
+ * Fails (see mlsl_last_error) unless op is MLSL_RT_SUM and dt is f32 or bf16,
+ * and for an unknown algo; it never runs an exact allreduce instead. */
+typedef enum { MLSL_QAR_RING = 0, MLSL_QAR_TWO_SHOT = 1 } mlsl_quant_ar_algo;
+int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
+                                              mlsl_data_type dt, mlsl_reduction op,
+                                              mlsl_group g, mlsl_quant_ar_algo algo,
+                                              mlsl_request* out);
 int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
                                    mlsl_data_type dt, mlsl_reduction op, mlsl_group g,
                                    mlsl_request* out);

@@ -20,6 +20,7 @@ void LaunchQuantAccum(void*, const void*, size_t, size_t, hipStream_t) STUB()
 void LaunchQuantSumDequant(const void*, const void*, void*, size_t, size_t, DataType, hipStream_t) STUB()
 void LaunchQuantSumDequantNT(const void*, const void*, void*, size_t, size_t, DataType, hipStream_t) STUB()
 void LaunchQuantSumDequantN(const void* const*, int, void*, size_t, size_t, DataType, hipStream_t) STUB()
+void LaunchQuantSumRequantN(const void* const*, int, void*, size_t, size_t, hipStream_t) STUB()
 void LaunchDequantizeSegments(const void*, size_t, void*, size_t, size_t, DataType, bool, hipStream_t) STUB()
 void LaunchPack(const void*, void*, const PackBlockDesc&, DataType, hipStream_t) STUB()
 void LaunchUnpack(const void*, void*, const PackBlockDesc&, DataType, hipStream_t) STUB()

@@ -43,6 +43,11 @@ def _lib():
                                                    c.c_void_p, c.c_size_t, c.c_size_t,
                                                    c.c_int]
         L.mlsl_host_quant_sum_dequant_n.argtypes = L.mlsl_hip_quant_sum_dequant_n.argtypes
+        L.mlsl_hip_quant_sum_requant_n.argtypes = [c.POINTER(c.c_void_p), c.c_int,
+                                                   c.c_void_p, c.c_size_t, c.c_size_t]
+        L.mlsl_host_quant_sum_requant_n.argtypes = L.mlsl_hip_quant_sum_requant_n.argtypes
+        L.mlsl_hip_quant_sum_requant_n.restype = c.c_int
+        L.mlsl_host_quant_sum_requant_n.restype = c.c_int
         L.mlsl_hip_dequantize_segments.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p,
                                                    c.c_size_t, c.c_size_t, c.c_int, c.c_int]
         L.mlsl_host_dequantize_segments.argtypes = L.mlsl_hip_dequantize_segments.argtypes
@@ -186,6 +191,19 @@ def quant_sum_dequant_n(wires, out, count, block=256, dtype=None):
                                               DTYPE[dt]))
 
 
+def quant_sum_requant_n(wires, dst, nunits, block=256):
+    """dst = requantize(the sum of dequantize(w) over the 1 to 8 `wires`), over
+    `nunits` whole wire units of block + 8 bytes: no element count and no
+    dtype. Per element the sum starts at +0 and takes one fma per wire, in the
+    order given; each block is requantized once, with `quantize`'s codec.
+    `dst` may be exactly one of the wires (the sum replaces it in place) or
+    overlap none of them. The owner's step of the two-shot quantized
+    all_reduce (ar_algo="two_shot")."""
+    ptrs = (ctypes.c_void_p * len(wires))(*[_as_ptr_dtype(w)[0].value for w in wires])
+    dp, _ = _as_ptr_dtype(dst)
+    check(_lib().mlsl_hip_quant_sum_requant_n(ptrs, len(wires), dp, nunits, block))
+
+
 def dequantize_segments(wire, out, count, nseg, block=256, dtype=None, accumulate=False):
     """The finish of the quantized all_gather in one launch: `wire` holds
     `nseg` segment wires of wire_bytes(count, block) bytes, each on a block
@@ -263,6 +281,16 @@ def host_quant_sum_dequant_n(wires, out, count, block=256, dtype="f32"):
     op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
     check(_lib().mlsl_host_quant_sum_dequant_n(ptrs, len(wires), op_, count, block,
                                                DTYPE[dtype]))
+
+
+def host_quant_sum_requant_n(wires, dst, nunits, block=256):
+    """Host twin of `quant_sum_requant_n` on numpy arrays: the same bits."""
+    _check_block(block)
+    need = nunits * (block + 8)
+    ptrs = (ctypes.c_void_p * len(wires))(
+        *[_host_buf(w, need, f"wires[{i}]").value for i, w in enumerate(wires)])
+    dp = _host_buf(dst, need, "dst")
+    check(_lib().mlsl_host_quant_sum_requant_n(ptrs, len(wires), dp, nunits, block))
 
 
 def host_dequantize_segments(wire, out, count, nseg, block=256, dtype="f32",
