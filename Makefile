@@ -183,6 +183,22 @@ $(ASAN_API): $(ASAN_SRC)
 	@mkdir -p $(dir $@)
 	g++ -O1 -g -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include 	    -fsanitize=address,undefined -fno-omit-frame-pointer 	    $(ASAN_SRC) -L/opt/rocm/lib -lrccl -lamdhip64 -pthread -o $@
 
+# The IPC-window schedule walker's launch sequence under ASan/UBSan: the real
+# schedules and plans through P2pGroup::IssueSchedule on a hand-built group,
+# every launcher recording its arguments (asan_kernel_stubs.cpp). Prints one
+# digest line per case and rank; tests/golden/p2p_issue_trace.txt pins them.
+P2P_TRACE := $(BUILD)/p2p_issue_trace_asan
+P2P_TRACE_SRC := $(CSRC) mlsl_amd/csrc/tests/p2p_issue_trace.cpp \
+    mlsl_amd/csrc/tests/asan_kernel_stubs.cpp
+
+p2p-trace: $(P2P_TRACE)
+
+$(P2P_TRACE): $(P2P_TRACE_SRC)
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
+	    -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $(P2P_TRACE_SRC) -L/opt/rocm/lib -lrccl -lamdhip64 -pthread -o $@
+
 TSAN_API := $(BUILD)/api_selftest_tsan
 
 tsan-api: $(TSAN_API)

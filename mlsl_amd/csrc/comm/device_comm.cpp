@@ -28,6 +28,7 @@
 #include "context.hpp"
 #include "p2p_transport.hpp"
 #include "quant.hpp"
+#include "device_local_op.hpp"
 #include "device_state.hpp"
 #include "group.hpp"
 #include "request.hpp"
@@ -451,7 +452,7 @@ bool RecvIsInput(CommRequest* req) {
 
 // Issue one chunk through the fused RCCL op set.
 void IssueFused(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
-                DeviceReqState& st, size_t tmp_off) {
+                DeviceReqState& st) {
     const OpSpec& spec = req->Spec();
     ProcessGroup* g = req->Group();
     const size_t es = DtypeSize(req->Dtype());
@@ -482,8 +483,7 @@ void IssueFused(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
             NCCL_CHECK(ncclReduce(sbase, rbase, cnt, ndt, nop, spec.root, comm, s));
             break;
         case CollOp::BCAST:
-            NCCL_CHECK(ncclBroadcast(g->MyIdx() == spec.root ? rbase : rbase, rbase,
-                                     cnt, ndt, spec.root, comm, s));
+            NCCL_CHECK(ncclBroadcast(rbase, rbase, cnt, ndt, spec.root, comm, s));
             break;
         case CollOp::REDUCE_SCATTER:
             NCCL_CHECK(ncclReduceScatter(sbase, rbase, spec.count, ndt, nop, comm, s));
@@ -578,7 +578,6 @@ void IssueFused(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
             break;
         }
     }
-    (void)tmp_off;
 }
 
 // Issue one chunk by walking its schedule: per phase a grouped
@@ -587,17 +586,8 @@ void IssueFused(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
 // transport, OUR schedule supplies the algorithm and OUR kernels the math.
 void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t s,
                    const uint8_t* sbase, uint8_t* rbase, uint8_t* tmp_dev) {
-    const size_t es = DtypeSize(req->Dtype());
     const ncclDataType_t ndt = ncclUint8;  // byte-addressed transfers
-
-    auto ptr = [&](const BufRef& b) -> uint8_t* {
-        switch (b.space) {
-            case Space::SEND: return const_cast<uint8_t*>(sbase) + b.off;
-            case Space::RECV: return rbase + b.off;
-            case Space::TMP: return tmp_dev + b.off;
-        }
-        return nullptr;
-    };
+    auto ptr = [&](const BufRef& b) { return SpacePtr(b, sbase, rbase, tmp_dev); };
 
     for (int phase = 0; phase < ce.sch.num_phases; ++phase) {
         bool grouped = false;
@@ -618,25 +608,10 @@ void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t
         for (const auto& st : ce.sch.steps) {
             if (st.phase != phase || st.local == Step::LocalOp::NONE) continue;
             if (st.local_dst.bytes == 0) continue;  // zero-length segment
-            uint8_t* d = ptr(st.local_dst);
-            uint8_t* src = ptr(st.local_src);
-            if (st.local == Step::LocalOp::COPY) {
-                if (d != src) LaunchCopy(d, src, st.local_src.bytes, s);
-            } else if (st.local == Step::LocalOp::SUMQ) {
-                // a compressed chunk's sbase is its plan's base (IssueAll)
-                const QuantPlan& p = ce.qplan;
-                uint8_t* base = const_cast<uint8_t*>(sbase);
-                const void* wires[kQuantRsDirectMaxRanks];
-                for (int k = 0; k < p.sumq_nwires; ++k) wires[k] = base + p.sumq_wire_off[k];
-                LaunchQuantSumRequantN(wires, p.sumq_nwires, base + p.sumq_dst_off,
-                                       p.sumq_units, p.block, s);
-            } else if (ce.sch.quant_block > 0) {
-                const size_t blk = ce.sch.quant_block;
-                const size_t units = st.local_dst.bytes / req->QParams().WireBlockBytes();
-                LaunchQuantAccum(d, src, units * blk, blk, s);
-            } else {
-                LaunchReduce(d, src, st.local_dst.bytes / es, req->Dtype(), ce.sch.rop, s);
-            }
+            // a compressed chunk's sbase is its plan's base (IssueAll)
+            LaunchLocalOp(st, ptr(st.local_dst), ptr(st.local_src), ce.qplan,
+                          const_cast<uint8_t*>(sbase), req->Dtype(), ce.sch.rop,
+                          req->QParams().WireBlockBytes(), s, /*nt=*/true);
         }
     }
 }
@@ -659,7 +634,7 @@ void IssueCompressed(CommRequest* req, const ChunkExec& ce, uint8_t* base,
                        p.residual, s);
     walk(base, base + p.scratch_off);
     const void* wires[kQuantRsDirectMaxRanks];
-    for (int k = 0; k < p.nwires; ++k) wires[k] = base + p.wire_off[k];
+    FinishWires(p, base, wires);
     switch (p.finish) {
         case QuantFinish::SUMN:
             LaunchQuantSumDequantN(wires, p.nwires, rbuf, p.count, p.block, dt, s);
@@ -926,7 +901,9 @@ void IssueAll(CommRequest* req, GroupComms& gc, DeviceReqState& st, const IssueC
         const size_t lane = !ic.p2p ? 0 : ic.prio ? gc.p2p->Lanes() - 1 : ch;
         ncclComm_t comm_ = ic.p2p ? nullptr : ic.prio ? gc.prio_comm : gc.comms[ch];
         auto walk = [&](const uint8_t* sbase, uint8_t* rbase, uint8_t* scratch) {
-            if (ic.p2p) gc.p2p->IssueSchedule(req, ce, lane, strm_, sbase, rbase, scratch);
+            if (ic.p2p)
+                gc.p2p->IssueSchedule(req->Dtype(), req->QParams().WireBlockBytes(), ce, lane,
+                                      strm_, sbase, rbase, scratch);
             else IssueSchedule(req, ce, comm_, strm_, sbase, rbase, scratch);
         };
         if (compressed) {
@@ -939,7 +916,7 @@ void IssueAll(CommRequest* req, GroupComms& gc, DeviceReqState& st, const IssueC
             walk(req->SendBuf() + ce.elem_off * es, req->RecvBuf() + ce.elem_off * es, tbase);
             tmp_off += ce.sch.tmp_bytes;
         } else {
-            IssueFused(req, ce, comm_, strm_, st, tmp_off);
+            IssueFused(req, ce, comm_, strm_, st);
             tmp_off += ce.sch.tmp_bytes;
         }
     }

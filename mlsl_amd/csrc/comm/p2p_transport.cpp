@@ -10,6 +10,7 @@
 #include "../hip/kernels.hpp"
 #include "bootstrap.hpp"
 #include "context.hpp"
+#include "device_local_op.hpp"
 #include "group.hpp"
 #include "request.hpp"
 
@@ -212,99 +213,232 @@ void P2pGroup::PublishFlag(void* mbox, uint64_t val, hipStream_t s) {
 
 // --- transport ops ---------------------------------------------------------
 
-void P2pGroup::IssueSchedule(CommRequest* req, ChunkExec& ce, size_t lane,
-                             hipStream_t s, const uint8_t* sbase,
-                             uint8_t* rbase, uint8_t* tmp) {
-    std::lock_guard<std::mutex> lk(g_issue_mu);
-    const size_t es = DtypeSize(req->Dtype());
-    const bool quant = ce.sch.quant_block > 0;
-    const size_t unit = quant ? req->QParams().WireBlockBytes() : es;
-    const size_t blk = ce.sch.quant_block;
-    MLSL_CHECK(lane < nlanes_, "p2p lane out of range");
+namespace {
+// How a step's receive is consumed. The fusion cases: the received data IS
+// the local op's source (ring/RHD reduce), or the local op targets the recv
+// range (reduce-scatter's out-of-place accumulate). Both are handled per
+// sub-message; any other local op runs unfused after the phase's traffic.
+enum class Consume { COPY, REDUCE_INTO, REDUCE_OUT };
 
-    auto ptr = [&](const BufRef& b) -> uint8_t* {
-        switch (b.space) {
-            case Space::SEND: return const_cast<uint8_t*>(sbase) + b.off;
-            case Space::RECV: return rbase + b.off;
-            case Space::TMP: return tmp + b.off;
+bool SameRef(const BufRef& a, const BufRef& b) {
+    return a.space == b.space && a.off == b.off && a.bytes == b.bytes;
+}
+bool HasRecv(const Step& st) { return st.recv_peer >= 0 && st.recv.bytes > 0; }
+Consume ConsumeOf(const Step& st) {
+    if (st.local != Step::LocalOp::REDUCE) return Consume::COPY;
+    if (SameRef(st.local_src, st.recv)) return Consume::REDUCE_INTO;
+    if (SameRef(st.local_dst, st.recv) && st.local_src.bytes == st.recv.bytes)
+        return Consume::REDUCE_OUT;
+    return Consume::COPY;
+}
+
+// Adaptive sub-message size: ~8 sub-messages per transfer (pipelines DMA
+// against the consumer's reduce) but never below 4 MiB (each wide-path
+// sub-message costs ~5 kernel launches) and never above the slot.
+// Sender and receiver derive the identical size from the transfer length,
+// so the slot partition always agrees.
+size_t SubSize(size_t bytes, size_t unit, size_t msg_max) {
+    size_t v = std::max<size_t>((bytes + 7) / 8, std::min<size_t>(4u << 20, msg_max));
+    v = std::min(v, msg_max);
+    v = (v / unit) * unit;
+    if (v < unit) v = unit;
+    return std::min(v, msg_max);
+}
+}  // namespace
+
+// What one IssueSchedule call holds fixed for its stages.
+struct P2pGroup::Walk {
+    const Schedule& sch;
+    DataType dtype;
+    size_t es, unit, blk;   // element bytes; sub-message granule; quant block (0: not compressed)
+    size_t msg_max;         // the slot, rounded down to whole units
+    size_t lane;
+    hipStream_t s;
+    const uint8_t* sbase;
+    uint8_t *rbase, *tmp;
+    bool Quant() const { return blk > 0; }
+    uint8_t* Ptr(const BufRef& b) const { return SpacePtr(b, sbase, rbase, tmp); }
+    // Sub-message k of a `bytes` transfer: false past its end.
+    bool Sub(size_t bytes, size_t k, size_t* off, size_t* n) const {
+        const size_t sub = SubSize(bytes, unit, msg_max);
+        *off = k * sub;
+        if (*off >= bytes) return false;
+        *n = std::min(sub, bytes - *off);
+        return true;
+    }
+    size_t NumSubs(size_t bytes) const {
+        const size_t sub = SubSize(bytes, unit, msg_max);
+        return (bytes + sub - 1) / sub;
+    }
+};
+
+P2pGroup::Edge P2pGroup::Advance(std::vector<uint64_t>& seqs, int peer, size_t lane) const {
+    const size_t idx = static_cast<size_t>(peer) * nlanes_ + lane;
+    const uint64_t seq = ++seqs[idx];
+    return {seq, (seq - 1) % nslots_, idx};
+}
+
+XferPoll P2pGroup::Poll(const void* mbox, uint64_t target) const {
+    return {mbox, target, abort_host_, status_host_, max_ticks_};
+}
+
+// One-shot (direct) allreduce fast path: the whole exchange phase becomes
+// TWO kernels — a fan-out pushing the payload to every peer and a fan-in
+// waiting all arrivals and reducing them in a single pass over dst. Declines
+// (false, nothing issued) for large payloads, >8 peers or uncovered dtypes:
+// the generic loop takes the phase then.
+bool P2pGroup::TryFanPhase(const Walk& w, int phase) {
+    if (!w.sch.one_shot || phase != 1 || w.Quant()) return false;
+    std::vector<const Step*> fan;
+    for (const auto& st : w.sch.steps)
+        if (st.phase == 1) fan.push_back(&st);
+    const size_t B = fan.empty() ? 0 : fan[0]->send.bytes;
+    const bool covered = w.dtype == DataType::F32 || w.dtype == DataType::BF16;
+    if (fan.empty() || fan.size() > 8 || B == 0 || B > w.msg_max || B > FusedMaxBytes() ||
+        !covered)
+        return false;
+    const XferPoll ab = Poll(nullptr, 0);
+    FanPeer sp[8], rp[8];
+    const int np = static_cast<int>(fan.size());
+    for (int i = 0; i < np; ++i) {
+        const int peer = fan[i]->send_peer;
+        const Edge se = NextSend(peer, w.lane);
+        sp[i].slot = PeerSlot(peer, w.lane, se.slot);
+        sp[i].flag = PeerInFlag(peer, w.lane);
+        sp[i].flag_val = se.seq;
+        sp[i].wait_mbox = se.seq > nslots_ ? MyAckFlag(peer, w.lane) : nullptr;
+        sp[i].wait_target = se.seq - nslots_;
+        sp[i].ctr = ctr_dev_ + se.idx;
+        sp[i].ctr_target = fused_sent_[se.idx] += static_cast<uint64_t>(FanOutWgsPerPeer(np));
+        const Edge re = NextRecv(peer, w.lane);
+        rp[i].slot = MySlot(peer, w.lane, re.slot);
+        rp[i].flag = PeerAckFlag(peer, w.lane);
+        rp[i].flag_val = re.seq;
+        rp[i].wait_mbox = MyInFlag(peer, w.lane);
+        rp[i].wait_target = re.seq;
+        rp[i].ctr = nullptr;
+        rp[i].ctr_target = 0;
+    }
+    LaunchFanOutSend(w.Ptr(fan[0]->send), B, sp, np, &ab, w.s);
+    uint64_t* fctr = ctr_dev_ + 2 * static_cast<size_t>(gsize_) * nlanes_ + w.lane;
+    const bool ok = LaunchFanInReduce(w.Ptr(fan[0]->local_dst), B / w.es, w.dtype, w.sch.rop, rp,
+                                      np, fctr, fanin_adds_[w.lane] += kXferFusedGrid, &ab, w.s);
+    MLSL_CHECK(ok, "fan-in dtype dispatch failed");
+    return true;
+}
+
+// Sub-message k of a step's send (nothing past the transfer's end).
+void P2pGroup::SendSub(const Walk& w, const Step& st, size_t k) {
+    size_t off, n;
+    if (!w.Sub(st.send.bytes, k, &off, &n)) return;
+    const int peer = st.send_peer;
+    const Edge e = NextSend(peer, w.lane);
+    uint8_t* slot = PeerSlot(peer, w.lane, e.slot);
+    // backpressure: the slot is free once the peer has acked its last use
+    const void* ack = e.seq > nslots_ ? MyAckFlag(peer, w.lane) : nullptr;
+    if (n <= FusedMaxBytes()) {
+        // Small sub-message: ONE bounded-grid kernel does the backpressure
+        // poll, the slot copy and the publish (32 workgroups can never
+        // starve the peer — the full-device fused variant deadlocked; see
+        // below).
+        const XferPoll bp = Poll(ack, e.seq - nslots_);
+        LaunchXferSendFused(slot, w.Ptr(st.send) + off, n, ack ? &bp : nullptr,
+                            ctr_dev_ + e.idx, fused_sent_[e.idx] += kXferFusedGrid,
+                            PeerInFlag(peer, w.lane), e.seq, w.s);
+        return;
+    }
+    // Backpressure (slot reuse) as a SEPARATE 1-wg wait kernel: a poll fused
+    // into a FULL-DEVICE copy kernel deadlocked two same-device ranks — each
+    // rank's spinner starved the peer's consumer kernel of CUs (measured at
+    // 256 MiB world-2). The 1-wg wait always co-schedules.
+    if (ack)
+        LaunchWaitFlag(ack, e.seq - nslots_, abort_host_, status_host_, max_ticks_, w.s);
+    LaunchXferCopy(slot, w.Ptr(st.send) + off, n, nullptr, w.s);
+    PublishFlag(PeerInFlag(peer, w.lane), e.seq, w.s);
+}
+
+// Sub-message k of a step's receive, consumed as ConsumeOf(st) says.
+void P2pGroup::RecvSub(const Walk& w, const Step& st, size_t k) {
+    const Consume c = ConsumeOf(st);
+    size_t off, n;
+    if (!w.Sub(st.recv.bytes, k, &off, &n)) return;
+    const int peer = st.recv_peer;
+    const Edge e = NextRecv(peer, w.lane);
+    const uint8_t* sl = MySlot(peer, w.lane, e.slot);
+    void* arrived = MyInFlag(peer, w.lane);
+    void* ack = PeerAckFlag(peer, w.lane);
+    const size_t qelems = w.Quant() ? (n / w.unit) * w.blk : 0;
+    if (n <= FusedMaxBytes()) {
+        // Small sub-message: the wait, the consume and the ack in one
+        // bounded-grid kernel.
+        const XferPoll wp = Poll(arrived, e.seq);
+        uint64_t* rctr = ctr_dev_ + static_cast<size_t>(gsize_) * nlanes_ + e.idx;
+        if (w.Quant() && c == Consume::REDUCE_INTO) {
+            // compressed-domain accumulate with the wait fused in
+            LaunchXferRecvQuantAccum(w.Ptr(st.local_dst) + off, sl, qelems, w.blk, &wp, rctr,
+                                     fused_rcvd_[e.idx] += kXferFusedGrid, ack, e.seq, w.s);
+            return;
         }
-        return nullptr;
-    };
-    auto same_ref = [](const BufRef& a, const BufRef& b) {
-        return a.space == b.space && a.off == b.off && a.bytes == b.bytes;
-    };
-
-    const size_t msg_max = (slot_bytes_ / unit) * unit;
-    MLSL_CHECK(msg_max > 0, "p2p slot smaller than one element/block");
-    // Adaptive sub-message size: ~8 sub-messages per transfer (pipelines
-    // DMA against the consumer's reduce) but never below 4 MiB (each
-    // wide-path sub-message costs ~5 kernel launches) and never above the
-    // slot.
-    // Sender and receiver derive the identical size from the transfer
-    // length, so the slot partition always agrees.
-    auto sub_size = [&](size_t bytes) -> size_t {
-        size_t v = std::max<size_t>((bytes + 7) / 8,
-                                    std::min<size_t>(4u << 20, msg_max));
-        v = std::min(v, msg_max);
-        v = (v / unit) * unit;
-        if (v < unit) v = unit;
-        return std::min(v, msg_max);
-    };
-    for (int phase = 0; phase < ce.sch.num_phases; ++phase) {
-        // One-shot (direct) allreduce fast path: the whole exchange phase
-        // becomes TWO kernels — a fan-out pushing the payload to every
-        // peer and a fan-in waiting all arrivals and reducing them in a
-        // single pass over dst. Falls back to the generic loop for large
-        // payloads, >8 peers or uncovered dtypes.
-        if (ce.sch.one_shot && phase == 1 && !quant) {
-            std::vector<const Step*> fan;
-            for (const auto& st : ce.sch.steps)
-                if (st.phase == 1) fan.push_back(&st);
-            const size_t B = fan.empty() ? 0 : fan[0]->send.bytes;
-            const bool covered = req->Dtype() == DataType::F32 ||
-                                 req->Dtype() == DataType::BF16;
-            if (!fan.empty() && fan.size() <= 8 && B > 0 && B <= msg_max &&
-                B <= FusedMaxBytes() && covered) {
-                XferPoll ab{};
-                ab.abort_word = abort_host_;
-                ab.status = status_host_;
-                ab.max_ticks = max_ticks_;
-                FanPeer sp[8], rp[8];
-                const int np = static_cast<int>(fan.size());
-                for (int i = 0; i < np; ++i) {
-                    const Step* st = fan[i];
-                    const int peer = st->send_peer;
-                    const size_t e = static_cast<size_t>(peer) * nlanes_ + lane;
-                    const uint64_t sseq = ++sent_[e];
-                    sp[i].slot = PeerSlot(peer, lane, (sseq - 1) % nslots_);
-                    sp[i].flag = PeerInFlag(peer, lane);
-                    sp[i].flag_val = sseq;
-                    sp[i].wait_mbox =
-                        sseq > nslots_ ? MyAckFlag(peer, lane) : nullptr;
-                    sp[i].wait_target = sseq - nslots_;
-                    sp[i].ctr = ctr_dev_ + e;
-                    sp[i].ctr_target =
-                        fused_sent_[e] += static_cast<uint64_t>(
-                            FanOutWgsPerPeer(static_cast<int>(fan.size())));
-                    const uint64_t rseq = ++rcvd_[e];
-                    rp[i].slot = MySlot(peer, lane, (rseq - 1) % nslots_);
-                    rp[i].flag = PeerAckFlag(peer, lane);
-                    rp[i].flag_val = rseq;
-                    rp[i].wait_mbox = MyInFlag(peer, lane);
-                    rp[i].wait_target = rseq;
-                    rp[i].ctr = nullptr;
-                    rp[i].ctr_target = 0;
-                }
-                LaunchFanOutSend(ptr(fan[0]->send), B, sp, np, &ab, s);
-                uint64_t* fctr =
-                    ctr_dev_ + 2 * static_cast<size_t>(gsize_) * nlanes_ + lane;
-                const bool ok = LaunchFanInReduce(
-                    ptr(fan[0]->local_dst), B / es, req->Dtype(), ce.sch.rop,
-                    rp, np, fctr, fanin_adds_[lane] += kXferFusedGrid, &ab, s);
-                MLSL_CHECK(ok, "fan-in dtype dispatch failed");
-                continue;
+        if (!w.Quant() || c == Consume::COPY) {
+            // COPY (byte copy) is dtype-agnostic, so quant AG forwards ride
+            // it too
+            const FusedConsume mode = c == Consume::REDUCE_INTO  ? FusedConsume::REDUCE
+                                      : c == Consume::REDUCE_OUT ? FusedConsume::REDUCE_OUT
+                                                                 : FusedConsume::COPY;
+            uint8_t* d = w.Ptr(c == Consume::REDUCE_INTO ? st.local_dst : st.recv) + off;
+            const uint8_t* o = c == Consume::REDUCE_OUT ? w.Ptr(st.local_src) + off : nullptr;
+            if (LaunchXferRecvFused(d, sl, o, c == Consume::COPY ? n : n / w.es, w.dtype,
+                                    w.sch.rop, mode, &wp, rctr,
+                                    fused_rcvd_[e.idx] += kXferFusedGrid, ack, e.seq, w.s))
+                return;
+            fused_rcvd_[e.idx] -= kXferFusedGrid;  // dtype not covered: nothing was launched
+        }
+    }
+    // Arrival wait as a 1-wg kernel (same deadlock avoidance as the sender
+    // backpressure), then the wide consume kernel, then the ack.
+    LaunchWaitFlag(arrived, e.seq, abort_host_, status_host_, max_ticks_, w.s);
+    switch (c) {
+        case Consume::COPY:
+            LaunchXferCopy(w.Ptr(st.recv) + off, sl, n, nullptr, w.s);
+            break;
+        case Consume::REDUCE_INTO: {
+            uint8_t* d = w.Ptr(st.local_dst) + off;
+            if (w.Quant())
+                LaunchQuantAccum(d, sl, qelems, w.blk, w.s);
+            else if (!LaunchXferReduce(d, sl, nullptr, n / w.es, w.dtype, w.sch.rop, nullptr, w.s))
+                LaunchReduce(d, sl, n / w.es, w.dtype, w.sch.rop, w.s);
+            break;
+        }
+        case Consume::REDUCE_OUT: {
+            uint8_t* d = w.Ptr(st.recv) + off;
+            const uint8_t* o = w.Ptr(st.local_src) + off;
+            if (w.Quant()) {
+                // acc = slot, then acc += local_src slice
+                LaunchCopyVariant(d, sl, n, false, w.s);
+                LaunchQuantAccum(d, o, qelems, w.blk, w.s);
+            } else if (!LaunchXferReduce(d, sl, o, n / w.es, w.dtype, w.sch.rop, nullptr, w.s)) {
+                LaunchReduceOut(d, sl, o, n / w.es, w.dtype, w.sch.rop, w.s);
             }
+            break;
         }
+    }
+    PublishFlag(ack, e.seq, w.s);
+}
+
+void P2pGroup::IssueSchedule(DataType dtype, size_t wire_unit, ChunkExec& ce, size_t lane,
+                             hipStream_t s, const uint8_t* sbase, uint8_t* rbase,
+                             uint8_t* tmp) {
+    std::lock_guard<std::mutex> lk(g_issue_mu);
+    MLSL_CHECK(lane < nlanes_, "p2p lane out of range");
+    const size_t es = DtypeSize(dtype);
+    const size_t blk = ce.sch.quant_block;
+    const size_t unit = blk > 0 ? wire_unit : es;
+    const Walk w{ce.sch, dtype, es,    unit,  blk, (slot_bytes_ / unit) * unit,
+                 lane,   s,     sbase, rbase, tmp};
+    MLSL_CHECK(w.msg_max > 0, "p2p slot smaller than one element/block");
+
+    for (int phase = 0; phase < ce.sch.num_phases; ++phase) {
+        if (TryFanPhase(w, phase)) continue;
         // Collect this phase's send and recv jobs, then interleave their
         // sub-messages round-robin. The interleave is what makes the
         // bounded slot ring deadlock-free: a sender blocked on backpressure
@@ -313,205 +447,36 @@ void P2pGroup::IssueSchedule(CommRequest* req, ChunkExec& ce, size_t lane,
         // enqueued at the previous sub-message index. Issuing all sends of
         // a phase before any recv would cycle-deadlock the ring whenever a
         // segment needs more sub-messages than there are slots.
-        struct RecvJob {
-            const Step* st;
-            bool fuse_into, fuse_out;
-        };
-        std::vector<const Step*> sends;
-        std::vector<RecvJob> recvs;
+        std::vector<const Step*> sends, recvs;
         size_t max_msgs = 0;
         for (const auto& st : ce.sch.steps) {
             if (st.phase != phase) continue;
             if (st.send_peer >= 0 && st.send.bytes > 0) {
                 MLSL_CHECK(st.send_peer != my_idx_, "p2p self-send in schedule");
-                const size_t sub = sub_size(st.send.bytes);
                 sends.push_back(&st);
-                max_msgs = std::max(max_msgs, (st.send.bytes + sub - 1) / sub);
+                max_msgs = std::max(max_msgs, w.NumSubs(st.send.bytes));
             }
-            if (st.recv_peer >= 0 && st.recv.bytes > 0) {
+            if (HasRecv(st)) {
                 MLSL_CHECK(st.recv_peer != my_idx_, "p2p self-recv in schedule");
-                // Fusion cases: the received data IS the local op's source
-                // (ring/RHD reduce), or the local op targets the recv range
-                // (reduce-scatter's out-of-place accumulate).
-                const bool fuse_into = st.local == Step::LocalOp::REDUCE &&
-                                       same_ref(st.local_src, st.recv);
-                const bool fuse_out = !fuse_into &&
-                                      st.local == Step::LocalOp::REDUCE &&
-                                      same_ref(st.local_dst, st.recv) &&
-                                      st.local_src.bytes == st.recv.bytes;
-                const size_t sub = sub_size(st.recv.bytes);
-                recvs.push_back({&st, fuse_into, fuse_out});
-                max_msgs = std::max(max_msgs, (st.recv.bytes + sub - 1) / sub);
+                recvs.push_back(&st);
+                max_msgs = std::max(max_msgs, w.NumSubs(st.recv.bytes));
             }
         }
         for (size_t k = 0; k < max_msgs; ++k) {
-            for (const Step* st : sends) {
-                const size_t sub = sub_size(st->send.bytes);
-                const size_t off = k * sub;
-                if (off >= st->send.bytes) continue;
-                const size_t n = std::min(sub, st->send.bytes - off);
-                const int peer = st->send_peer;
-                uint64_t& sent = sent_[static_cast<size_t>(peer) * nlanes_ + lane];
-                const uint64_t seq = ++sent;
-                const size_t slot = (seq - 1) % nslots_;
-                if (n <= FusedMaxBytes()) {
-                    // Small sub-message: ONE bounded-grid kernel does the
-                    // backpressure poll, the slot copy and the publish
-                    // (32 workgroups can never starve the peer — the
-                    // full-device fused variant deadlocked; see below).
-                    const size_t e = static_cast<size_t>(peer) * nlanes_ + lane;
-                    XferPoll bp{};
-                    bp.mbox = seq > nslots_ ? MyAckFlag(peer, lane) : nullptr;
-                    bp.target = seq - nslots_;
-                    bp.abort_word = abort_host_;
-                    bp.status = status_host_;
-                    bp.max_ticks = max_ticks_;
-                    LaunchXferSendFused(PeerSlot(peer, lane, slot),
-                                        ptr(st->send) + off, n,
-                                        bp.mbox ? &bp : nullptr, ctr_dev_ + e,
-                                        fused_sent_[e] += kXferFusedGrid,
-                                        PeerInFlag(peer, lane), seq, s);
-                    continue;
-                }
-                // Backpressure (slot reuse) as a SEPARATE 1-wg wait kernel:
-                // a poll fused into a FULL-DEVICE copy kernel deadlocked two
-                // same-device ranks — each rank's spinner starved the
-                // peer's consumer kernel of CUs (measured at 256 MiB
-                // world-2). The 1-wg wait always co-schedules.
-                if (seq > nslots_)
-                    LaunchWaitFlag(MyAckFlag(peer, lane), seq - nslots_,
-                                   abort_host_, status_host_, max_ticks_, s);
-                LaunchXferCopy(PeerSlot(peer, lane, slot), ptr(st->send) + off,
-                               n, nullptr, s);
-                PublishFlag(PeerInFlag(peer, lane), seq, s);
-            }
-            for (const RecvJob& rj : recvs) {
-                const Step& st = *rj.st;
-                const size_t sub = sub_size(st.recv.bytes);
-                const size_t off = k * sub;
-                if (off >= st.recv.bytes) continue;
-                const size_t n = std::min(sub, st.recv.bytes - off);
-                const int peer = st.recv_peer;
-                uint64_t& rcvd = rcvd_[static_cast<size_t>(peer) * nlanes_ + lane];
-                const uint64_t seq = ++rcvd;
-                const size_t slot = (seq - 1) % nslots_;
-                const uint8_t* sl = MySlot(peer, lane, slot);
-                XferPoll wp{};
-                wp.mbox = MyInFlag(peer, lane);
-                wp.target = seq;
-                wp.abort_word = abort_host_;
-                wp.status = status_host_;
-                wp.max_ticks = max_ticks_;
-                if (n <= FusedMaxBytes()) {
-                    const size_t e = static_cast<size_t>(peer) * nlanes_ + lane;
-                    uint64_t* rctr = ctr_dev_ +
-                                     static_cast<size_t>(gsize_) * nlanes_ + e;
-                    if (quant && rj.fuse_into) {
-                        // compressed-domain accumulate with the wait fused in
-                        LaunchXferRecvQuantAccum(
-                            ptr(st.local_dst) + off, sl, (n / unit) * blk, blk,
-                            &wp, rctr, fused_rcvd_[e] += kXferFusedGrid,
-                            PeerAckFlag(peer, lane), seq, s);
-                        continue;
-                    }
-                    if (!quant || (!rj.fuse_into && !rj.fuse_out)) {
-                        // COPY (byte copy) is dtype-agnostic, so quant AG
-                        // forwards ride it too
-                        const FusedConsume mode =
-                            rj.fuse_into  ? FusedConsume::REDUCE
-                            : rj.fuse_out ? FusedConsume::REDUCE_OUT
-                                          : FusedConsume::COPY;
-                        uint8_t* d = mode == FusedConsume::REDUCE
-                                         ? ptr(st.local_dst) + off
-                                         : ptr(st.recv) + off;
-                        const uint8_t* o = mode == FusedConsume::REDUCE_OUT
-                                               ? ptr(st.local_src) + off
-                                               : nullptr;
-                        if (LaunchXferRecvFused(d, sl, o,
-                                                mode == FusedConsume::COPY ? n : n / es,
-                                                req->Dtype(), ce.sch.rop, mode,
-                                                &wp, rctr,
-                                                fused_rcvd_[e] += kXferFusedGrid,
-                                                PeerAckFlag(peer, lane), seq, s))
-                            continue;
-                        fused_rcvd_[e] -= kXferFusedGrid;  // dtype not covered
-                    }
-                }
-                // Arrival wait as a 1-wg kernel (same deadlock avoidance as
-                // the sender backpressure), then the wide consume kernel.
-                LaunchWaitFlag(MyInFlag(peer, lane), seq, abort_host_,
-                               status_host_, max_ticks_, s);
-                if (rj.fuse_into && !quant &&
-                    LaunchXferReduce(ptr(st.local_dst) + off, sl, nullptr,
-                                     n / es, req->Dtype(), ce.sch.rop, nullptr,
-                                     s)) {
-                } else if (rj.fuse_out && !quant &&
-                           LaunchXferReduce(ptr(st.recv) + off, sl,
-                                            ptr(st.local_src) + off, n / es,
-                                            req->Dtype(), ce.sch.rop, nullptr,
-                                            s)) {
-                } else if (!rj.fuse_into && !rj.fuse_out) {
-                    LaunchXferCopy(ptr(st.recv) + off, sl, n, nullptr, s);
-                } else {
-                    if (rj.fuse_into) {
-                        if (quant)
-                            LaunchQuantAccum(ptr(st.local_dst) + off, sl,
-                                             (n / unit) * blk, blk, s);
-                        else
-                            LaunchReduce(ptr(st.local_dst) + off, sl, n / es,
-                                         req->Dtype(), ce.sch.rop, s);
-                    } else {  // fuse_out
-                        if (quant) {
-                            // acc = slot, then acc += local_src slice
-                            LaunchCopyVariant(ptr(st.recv) + off, sl, n, false, s);
-                            LaunchQuantAccum(ptr(st.recv) + off,
-                                             ptr(st.local_src) + off,
-                                             (n / unit) * blk, blk, s);
-                        } else {
-                            LaunchReduceOut(ptr(st.recv) + off, sl,
-                                            ptr(st.local_src) + off, n / es,
-                                            req->Dtype(), ce.sch.rop, s);
-                        }
-                    }
-                }
-                PublishFlag(PeerAckFlag(peer, lane), seq, s);
-            }
+            for (const Step* st : sends) SendSub(w, *st, k);
+            for (const Step* st : recvs) RecvSub(w, *st, k);
         }
         // Unfused local ops (pure copy steps, or reduce with unrelated
         // source/dest geometry) run after the phase's traffic, step order.
         for (const auto& st : ce.sch.steps) {
             if (st.phase != phase || st.local == Step::LocalOp::NONE) continue;
             if (st.local_dst.bytes == 0) continue;  // zero-length segment
-            const bool was_recv_step = st.recv_peer >= 0 && st.recv.bytes > 0;
-            if (was_recv_step) {
-                const bool fuse_into = st.local == Step::LocalOp::REDUCE &&
-                                       same_ref(st.local_src, st.recv);
-                const bool fuse_out = !fuse_into &&
-                                      st.local == Step::LocalOp::REDUCE &&
-                                      same_ref(st.local_dst, st.recv) &&
-                                      st.local_src.bytes == st.recv.bytes;
-                if (fuse_into || fuse_out) continue;  // handled per sub-msg
-            }
-            uint8_t* d = ptr(st.local_dst);
-            uint8_t* src = ptr(st.local_src);
-            if (st.local == Step::LocalOp::COPY) {
-                if (d != src) LaunchCopyVariant(d, src, st.local_src.bytes, false, s);
-            } else if (st.local == Step::LocalOp::SUMQ) {
-                // a compressed chunk's sbase is its plan's base; the arrival
-                // slots were filled by this stream's consume kernels above
-                const QuantPlan& p = ce.qplan;
-                uint8_t* base = const_cast<uint8_t*>(sbase);
-                const void* wires[kQuantRsDirectMaxRanks];
-                for (int k = 0; k < p.sumq_nwires; ++k) wires[k] = base + p.sumq_wire_off[k];
-                LaunchQuantSumRequantN(wires, p.sumq_nwires, base + p.sumq_dst_off,
-                                       p.sumq_units, p.block, s);
-            } else if (quant) {
-                LaunchQuantAccum(d, src, (st.local_dst.bytes / unit) * blk,
-                                 blk, s);
-            } else {
-                LaunchReduce(d, src, st.local_dst.bytes / es, req->Dtype(),
-                             ce.sch.rop, s);
-            }
+            if (HasRecv(st) && ConsumeOf(st) != Consume::COPY) continue;  // done per sub-message
+            // a compressed chunk's sbase is its plan's base; the arrival
+            // slots were filled by this stream's consume kernels above
+            LaunchLocalOp(st, w.Ptr(st.local_dst), w.Ptr(st.local_src), ce.qplan,
+                          const_cast<uint8_t*>(sbase), dtype, ce.sch.rop, wire_unit, s,
+                          /*nt=*/false);
         }
     }
 }

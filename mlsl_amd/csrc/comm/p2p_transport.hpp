@@ -50,8 +50,8 @@
 namespace mlsl {
 
 class ProcessGroup;
-class CommRequest;
 struct ChunkExec;
+struct XferPoll;
 
 class P2pGroup {
   public:
@@ -64,12 +64,16 @@ class P2pGroup {
     size_t Lanes() const { return nlanes_; }
     size_t SlotBytes() const { return slot_bytes_; }
 
-    // Enqueue one schedule-step send/recv pair set onto `stream`.
-    // `sbase`/`rbase`/`tmp` resolve the chunk's SEND/RECV/TMP spaces.
-    // Throws on malformed schedules; device-side failures surface through
-    // CheckHealthy().
-    void IssueSchedule(CommRequest* req, ChunkExec& ce, size_t lane,
-                       hipStream_t stream, const uint8_t* sbase,
+    // Enqueue one chunk's whole schedule onto `stream`, phase by phase: the
+    // one-shot fan kernels where they apply (TryFanPhase), else the phase's
+    // sends and receives interleaved sub-message by sub-message (SendSub,
+    // RecvSub), then its unfused local ops. `dtype` is the request's, not
+    // sch.dtype; `wire_unit` the bytes of one wire block of a compressed
+    // chunk (unused otherwise). `sbase`/`rbase`/`tmp` resolve the chunk's
+    // SEND/RECV/TMP spaces. Throws on malformed schedules; device-side
+    // failures surface through Healthy().
+    void IssueSchedule(DataType dtype, size_t wire_unit, ChunkExec& ce,
+                       size_t lane, hipStream_t stream, const uint8_t* sbase,
                        uint8_t* rbase, uint8_t* tmp);
 
     // Host-side failure check: true while no wait kernel has aborted or
@@ -111,6 +115,22 @@ class P2pGroup {
     // be aborted, so a dead peer would wedge the queue forever.
     bool hw_write_ = false;
     void PublishFlag(void* mbox, uint64_t val, hipStream_t s);
+
+    // Stages of IssueSchedule (p2p_transport.cpp).
+    struct Walk;   // what one call holds fixed
+    // The next sub-message on (peer, lane): its sequence number (from 1), its
+    // slot, and the edge's index into the counters.
+    struct Edge {
+        uint64_t seq;
+        size_t slot, idx;
+    };
+    Edge Advance(std::vector<uint64_t>& seqs, int peer, size_t lane) const;
+    Edge NextSend(int peer, size_t lane) { return Advance(sent_, peer, lane); }
+    Edge NextRecv(int peer, size_t lane) { return Advance(rcvd_, peer, lane); }
+    XferPoll Poll(const void* mbox, uint64_t target) const;
+    bool TryFanPhase(const Walk& w, int phase);
+    void SendSub(const Walk& w, const Step& st, size_t k);
+    void RecvSub(const Walk& w, const Step& st, size_t k);
     friend class P2pGroupTestPeek;
 };
 

@@ -85,4 +85,16 @@ struct QuantPlan {
 QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t count,
                         size_t elem_size, QuantGather gather = QuantGather::NONE);
 
+// The plan's wire tables as pointers from the chunk base `base`, for the
+// N-way kernels and their host twins: the finish's nwires, the SUMQ step's
+// sumq_nwires. Entries past those counts are left alone.
+inline void FinishWires(const QuantPlan& p, const uint8_t* base,
+                        const void* (&wires)[kQuantRsDirectMaxRanks]) {
+    for (int k = 0; k < p.nwires; ++k) wires[k] = base + p.wire_off[k];
+}
+inline void SumqWires(const QuantPlan& p, const uint8_t* base,
+                      const void* (&wires)[kQuantRsDirectMaxRanks]) {
+    for (int k = 0; k < p.sumq_nwires; ++k) wires[k] = base + p.sumq_wire_off[k];
+}
+
 }  // namespace mlsl

@@ -694,8 +694,7 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                             // requantized once into the own range (refused
                             // with a plugin at Setup)
                             const void* in[kQuantRsDirectMaxRanks];
-                            for (int k = 0; k < qp.sumq_nwires; ++k)
-                                in[k] = wire + qp.sumq_wire_off[k];
+                            SumqWires(qp, wire, in);
                             if (qp.sumq_units > 0)
                                 HostQuantSumRequantN(in, qp.sumq_nwires,
                                                      wire + qp.sumq_dst_off, qp.sumq_units,
@@ -728,7 +727,7 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                     // requantizes the sum into the arrival slot first. (The
                     // one-shot schedule is refused with a plugin at Setup.)
                     const void* wires[kQuantRsDirectMaxRanks];
-                    for (int k = 0; k < qp.nwires; ++k) wires[k] = wire + qp.wire_off[k];
+                    FinishWires(qp, wire, wires);
                     if (plugin_) {
                         uint8_t* res = wire + qp.wire_off[0];
                         int rc = qp.finish == QuantFinish::SUM2
