@@ -161,6 +161,21 @@ $(ASAN_QAR_TWOSHOT): mlsl_amd/csrc/tests/quant_ar_twoshot_selftest.cpp mlsl_amd/
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -ldl -o $@
 
+# The codec over a list of tensors under ASan/UBSan: the gather and scatter
+# host twins over every segment layout with each tensor an exact-size heap
+# allocation, and the ring and two-shot exchanges walked by hand inside
+# plan-sized buffers between them, three starts with the residual carried.
+# Pure host C++, like the targets above.
+ASAN_QSEG := $(BUILD)/quant_seg_selftest_asan
+
+asan-quant-seg: $(ASAN_QSEG)
+	$(ASAN_QSEG)
+
+$(ASAN_QSEG): mlsl_amd/csrc/tests/quant_seg_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/comm/quant_plan.cpp mlsl_amd/csrc/core/log.cpp
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $^ -pthread -ldl -o $@
+
 # What a compressed all-gather request refuses at Setup(), through the C++
 # classes and the library as built (no sanitizer; world 1 over TCP).
 QAG_REQUEST := $(BUILD)/quant_ag_request_selftest

@@ -520,6 +520,83 @@ class PersistentRequest:
             self._h = None
 
 
+class SegmentedAllReduce:
+    """The int8-quantized all_reduce (a sum) over a LIST of tensors, in
+    place: the quantized all_reduce of their concatenation, which is never
+    built. The quantize prologue reads the tensors where they lie, and the
+    finish writes ``post_scale`` times the reduced values back into each:
+    ``(q * scale) * post_scale``, both products rounded to float32 (two
+    roundings: ``post_scale=1/world`` is not bit for bit a division
+    afterwards). Bit for bit that is the flat quantized request's result
+    times ``float32(post_scale)``, rounded to the dtype: for bf16,
+    ``q * scale`` is rounded to bf16 before it is scaled. The error-feedback
+    residual is kept across starts, flat, in concatenation order.
+
+    counts: elements per tensor, each >= 1; dtype "f32" or "bf16".
+    ar_algo: None takes MLSL_QUANT_AR_ALGO (ring unless set); "ring" or
+    "two_shot" names it (two_shot: at most 8 ranks).
+    Refused at creation: any other dtype, an empty list, a zero count, a
+    compression plugin. One bucket of DistributedData(compression="int8") is
+    one such request."""
+
+    def __init__(self, dist, counts, dtype="f32", group="global", ar_algo=None,
+                 post_scale=1.0):
+        if ar_algo is not None and ar_algo not in QUANT_AR_ALGO:
+            raise ValueError(f"ar_algo={ar_algo!r}: expected None, 'ring' or 'two_shot'")
+        L = lib()
+        if not hasattr(L, "_segments_declared"):
+            P = ctypes.POINTER
+            L.mlsl_persistent_all_reduce_quantized_segments.argtypes = [
+                c_void_p, P(c_size_t), c_size_t, c_int, c_int, c_int, ctypes.c_float,
+                P(c_void_p)]
+            L.mlsl_request_start_segments.argtypes = [c_void_p, P(c_void_p), c_size_t]
+            L.mlsl_request_wait.argtypes = [c_void_p, P(c_void_p)]
+            L.mlsl_request_test.argtypes = [c_void_p, P(c_int)]
+            L.mlsl_request_destroy.argtypes = [c_void_p]
+            for n in ("mlsl_persistent_all_reduce_quantized_segments",
+                      "mlsl_request_start_segments", "mlsl_request_wait",
+                      "mlsl_request_test", "mlsl_request_destroy"):
+                getattr(L, n).restype = c_int
+            L._segments_declared = True
+        counts = [int(n) for n in counts]
+        self._h = None
+        self.nseg = len(counts)
+        h = c_void_p()
+        check(L.mlsl_persistent_all_reduce_quantized_segments(
+            dist._h, _sizes(counts), len(counts), DTYPE[dtype], GROUP[group],
+            -1 if ar_algo is None else QUANT_AR_ALGO[ar_algo], post_scale,
+            ctypes.byref(h)))
+        self._h = h
+        self._ptrs = (c_void_p * max(1, len(counts)))()
+
+    def start(self, tensors):
+        """tensors: torch tensors (CPU, or device tensors in device mode),
+        numpy arrays or raw pointers, one per count and in that order; their
+        addresses may change from one start to the next."""
+        n = len(tensors)
+        if n == self.nseg:
+            for j, t in enumerate(tensors):
+                self._ptrs[j] = _as_ptr_dtype(t)[0].value
+            arr = self._ptrs
+        else:
+            # the library refuses it, by message
+            arr = (c_void_p * max(1, n))(*[_as_ptr_dtype(t)[0].value for t in tensors])
+        check(lib().mlsl_request_start_segments(self._h, arr, n))
+
+    def wait(self):
+        check(lib().mlsl_request_wait(self._h, None))
+
+    def test(self):
+        done = c_int(0)
+        check(lib().mlsl_request_test(self._h, ctypes.byref(done)))
+        return bool(done.value)
+
+    def destroy(self):
+        if self._h:
+            check(lib().mlsl_request_destroy(self._h))
+            self._h = None
+
+
 class CommBlockInfo:
     def __init__(self, handle):
         self._h = handle

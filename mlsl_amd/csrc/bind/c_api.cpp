@@ -270,6 +270,34 @@ int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
     C_CATCH
 }
 
+int mlsl_persistent_all_reduce_quantized_segments(mlsl_distribution d, const size_t* counts,
+                                                  size_t nseg, mlsl_data_type dt,
+                                                  mlsl_group g, int algo, float post_scale,
+                                                  mlsl_request* out) {
+    C_TRY
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized all_reduce over a tensor list supports f32/bf16 only");
+    MLSL_CHECK(nseg > 0 && counts != nullptr,
+               "quantized all_reduce over a tensor list needs at least one tensor "
+               "(nseg == 0)");
+    MLSL_CHECK(algo >= -1 && algo <= 1, "unknown quantized all_reduce algorithm");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddAllReduceSegments(std::vector<size_t>(counts, counts + nseg), post_scale);
+    r->SetCompression(Compression::QUANT_INT8,
+                      Environment::GetEnv().GetQuantizationParams());
+    // -1 names no algorithm: MLSL_QUANT_AR_ALGO decides at Setup()
+    if (algo >= 0)
+        r->SetQuantArAlgo(algo == 1 ? QuantArAlgo::TWO_SHOT : QuantArAlgo::RING);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
+int mlsl_request_start_segments(mlsl_request req, void* const* ptrs, size_t nseg) {
+    C_TRY static_cast<CommRequest*>(req)->StartSegments(ptrs, nseg);
+    C_CATCH
+}
+
 int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
                                    mlsl_data_type dt, mlsl_reduction op, mlsl_group g,
                                    mlsl_request* out) {

@@ -4,6 +4,9 @@
 // internally.
 #include <hip/hip_runtime.h>
 
+#include <string>
+#include <vector>
+
 #include "../comm/context.hpp"
 #include "../comm/device_comm.hpp"
 #include "../comm/quant.hpp"
@@ -150,6 +153,121 @@ int mlsl_hip_dequantize_segments(const void* wire, size_t nseg, void* out, size_
     OPS_TRY LaunchDequantizeSegments(wire, nseg, out, count, block,
                                      static_cast<DataType>(dt), accumulate != 0, nullptr);
     SyncNullStream();
+    OPS_CATCH
+}
+
+}  // extern "C"
+
+namespace {
+
+// Prefix offsets of `counts`, every count checked; the total in *count.
+std::vector<uint64_t> SegOffsets(const size_t* counts, size_t nseg, size_t* count,
+                                 const char* where) {
+    if (nseg == 0 || counts == nullptr)
+        throw Error(std::string(where) + " takes at least one segment");
+    std::vector<uint64_t> offs(nseg + 1, 0);
+    for (size_t j = 0; j < nseg; ++j) {
+        if (counts[j] == 0)
+            throw Error(std::string(where) + ": segment " + std::to_string(j) + " is empty");
+        offs[j + 1] = offs[j] + counts[j];
+    }
+    *count = offs[nseg];
+    return offs;
+}
+
+// Both segment tables in one device allocation, for one synchronous op.
+struct DevSegTables {
+    void* mem = nullptr;
+    const uint64_t* offs = nullptr;
+    void** ptrs = nullptr;
+    DevSegTables(const std::vector<uint64_t>& h_offs, const void* const* h_ptrs) {
+        const size_t nseg = h_offs.size() - 1;
+        const size_t ob = h_offs.size() * sizeof(uint64_t), pb = nseg * sizeof(void*);
+        if (hipMalloc(&mem, ob + pb) != hipSuccess) throw Error("hipMalloc of segment tables");
+        if (hipMemcpy(mem, h_offs.data(), ob, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(static_cast<uint8_t*>(mem) + ob, h_ptrs, pb, hipMemcpyHostToDevice) !=
+                hipSuccess) {
+            (void)hipFree(mem);
+            throw Error("hipMemcpy of segment tables");
+        }
+        offs = static_cast<const uint64_t*>(mem);
+        ptrs = reinterpret_cast<void**>(static_cast<uint8_t*>(mem) + ob);
+    }
+    ~DevSegTables() { (void)hipFree(mem); }
+    DevSegTables(const DevSegTables&) = delete;
+    DevSegTables& operator=(const DevSegTables&) = delete;
+};
+
+}  // namespace
+
+extern "C" {
+
+// The list-of-tensors codec: `ptrs` and `counts` are HOST arrays of nseg
+// entries (device pointers in the hip variants, which upload both tables).
+int mlsl_hip_quantize_gather(const void* const* ptrs, const size_t* counts, size_t nseg,
+                             void* err, void* wire, size_t block, int dt, int use_err) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_hip_quantize_gather");
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "quantize-gather");
+    DevSegTables tab(offs, ptrs);
+    LaunchQuantizeGather(tab.ptrs, tab.offs, nseg, err, wire, count, block,
+                         static_cast<DataType>(dt), use_err != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_dequantize_scatter(const void* wire, void* const* ptrs, const size_t* counts,
+                                size_t nseg, size_t block, int dt, float post_scale,
+                                int round_first) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_hip_dequantize_scatter");
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "dequantize-scatter");
+    DevSegTables tab(offs, ptrs);
+    LaunchDequantizeScatter(wire, tab.ptrs, tab.offs, nseg, count, block,
+                            static_cast<DataType>(dt), post_scale, round_first != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+// The same two kernels over tables that already are in device memory (nseg + 1
+// prefix offsets, nseg pointers), as a request keeps them: no upload here.
+int mlsl_hip_quantize_gather_tables(const void* const* dev_ptrs, const uint64_t* dev_offs,
+                                    size_t nseg, void* err, void* wire, size_t count,
+                                    size_t block, int dt, int use_err) {
+    OPS_TRY LaunchQuantizeGather(dev_ptrs, dev_offs, nseg, err, wire, count, block,
+                                 static_cast<DataType>(dt), use_err != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_dequantize_scatter_tables(const void* wire, void* const* dev_ptrs,
+                                       const uint64_t* dev_offs, size_t nseg, size_t count,
+                                       size_t block, int dt, float post_scale,
+                                       int round_first) {
+    OPS_TRY LaunchDequantizeScatter(wire, dev_ptrs, dev_offs, nseg, count, block,
+                                    static_cast<DataType>(dt), post_scale, round_first != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_host_quantize_gather(const void* const* ptrs, const size_t* counts, size_t nseg,
+                              void* err, void* wire, size_t block, int dt, int use_err) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_quantize_gather");
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "quantize-gather");
+    HostQuantizeGather(ptrs, offs.data(), nseg, err, wire, count, block,
+                       static_cast<DataType>(dt), use_err != 0);
+    OPS_CATCH
+}
+
+int mlsl_host_dequantize_scatter(const void* wire, void* const* ptrs, const size_t* counts,
+                                 size_t nseg, size_t block, int dt, float post_scale,
+                                 int round_first) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_dequantize_scatter");
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "dequantize-scatter");
+    HostDequantizeScatter(wire, ptrs, offs.data(), nseg, count, block,
+                          static_cast<DataType>(dt), post_scale, round_first != 0);
     OPS_CATCH
 }
 

@@ -66,6 +66,8 @@ DeviceReqState::~DeviceReqState() {
     rel(tmp_dev);
     rel(stage_send);
     rel(stage_recv);
+    rel(seg_dev);
+    if (seg_ptrs_pin) (void)hipHostFree(seg_ptrs_pin);
     if (pin_send) (void)hipHostFree(pin_send);
     if (pin_recv) (void)hipHostFree(pin_recv);
 }
@@ -353,6 +355,17 @@ void DeviceSetupRequest(CommRequest* req, DeviceReqState& st) {
         // zero once: error-feedback residuals must start clean
         HIP_CHECKD(hipMemset(st.tmp_dev, 0, tmp));
     }
+    if (req->Segmented()) {
+        const std::vector<uint64_t>& offs = req->SegOffs();
+        const size_t nseg = offs.size() - 1;
+        st.seg_dev = Context::Get().Device()->AllocDevice(offs.size() * sizeof(uint64_t) +
+                                                          nseg * sizeof(void*));
+        HIP_CHECKD(hipMemcpy(st.seg_dev, offs.data(), offs.size() * sizeof(uint64_t),
+                             hipMemcpyHostToDevice));
+        void* pin = nullptr;
+        HIP_CHECKD(hipHostMalloc(&pin, nseg * sizeof(void*)));
+        st.seg_ptrs_pin = static_cast<void**>(pin);
+    }
 }
 
 namespace {
@@ -622,16 +635,36 @@ void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t
 // run the schedule over the wire; finish into rbuf. `walk` is the only thing
 // the executors differ in: nothing at n=1, the IPC window walker, or the
 // RCCL one.
+// A request over a tensor list (one plan segment, a DEQUANT finish) has no
+// sbuf or rbuf: its prologue and finish go through the tables in `st`.
 template <class Walk>
-void IssueCompressed(CommRequest* req, const ChunkExec& ce, uint8_t* base,
-                     const uint8_t* sbuf, uint8_t* rbuf, hipStream_t s, Walk&& walk) {
+void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec& ce,
+                     uint8_t* base, const uint8_t* sbuf, uint8_t* rbuf, hipStream_t s,
+                     Walk&& walk) {
     const QuantPlan& p = ce.qplan;
     const DataType dt = req->Dtype();
-    for (size_t j = 0; j < p.nseg; ++j)
-        LaunchQuantize(sbuf + j * p.seg_bytes,
-                       p.residual ? base + p.err_off + j * p.seg_bytes : nullptr,
-                       base + (p.send_seg + j) * p.seg_wire, p.count, p.block, dt,
-                       p.residual, s);
+    const bool seg = req->Segmented();
+    const size_t nseg = seg ? req->SegPtrs().size() : 0;
+    const uint64_t* seg_offs = static_cast<const uint64_t*>(st.seg_dev);
+    void** seg_ptrs = seg ? reinterpret_cast<void**>(
+                                static_cast<uint8_t*>(st.seg_dev) + (nseg + 1) * sizeof(uint64_t))
+                          : nullptr;
+    if (seg) {
+        // this start's pointers, pinned host to device on the request's
+        // stream; the last start was waited for, so the mirror is free
+        std::memcpy(st.seg_ptrs_pin, req->SegPtrs().data(), nseg * sizeof(void*));
+        HIP_CHECKD(hipMemcpyAsync(seg_ptrs, st.seg_ptrs_pin, nseg * sizeof(void*),
+                                  hipMemcpyHostToDevice, s));
+        LaunchQuantizeGather(seg_ptrs, seg_offs, nseg, p.residual ? base + p.err_off : nullptr,
+                             base + p.send_seg * p.seg_wire, p.count, p.block, dt, p.residual,
+                             s);
+    } else {
+        for (size_t j = 0; j < p.nseg; ++j)
+            LaunchQuantize(sbuf + j * p.seg_bytes,
+                           p.residual ? base + p.err_off + j * p.seg_bytes : nullptr,
+                           base + (p.send_seg + j) * p.seg_wire, p.count, p.block, dt,
+                           p.residual, s);
+    }
     walk(base, base + p.scratch_off);
     const void* wires[kQuantRsDirectMaxRanks];
     FinishWires(p, base, wires);
@@ -643,7 +676,12 @@ void IssueCompressed(CommRequest* req, const ChunkExec& ce, uint8_t* base,
             LaunchQuantSumDequant(wires[0], wires[1], rbuf, p.count, p.block, dt, s);
             break;
         case QuantFinish::DEQUANT:
-            LaunchDequantize(wires[0], rbuf, p.count, p.block, dt, s);
+            if (seg)
+                // round_first: the flat request's bits, then scaled
+                LaunchDequantizeScatter(wires[0], seg_ptrs, seg_offs, nseg, p.count, p.block,
+                                        dt, req->PostScale(), /*round_first=*/true, s);
+            else
+                LaunchDequantize(wires[0], rbuf, p.count, p.block, dt, s);
             break;
         case QuantFinish::SCATTER:
             LaunchDequantizeSegments(wires[0], p.out_segs, rbuf, p.count, p.block, dt,
@@ -655,6 +693,9 @@ void IssueCompressed(CommRequest* req, const ChunkExec& ce, uint8_t* base,
 bool GraphEligible(CommRequest* req, GroupComms& gc) {
     // Single effective stream only: every chunk must land on channel 0 and
     // no host staging (H2D/D2H of *pageable* memory is not capturable).
+    // a tensor list's pointers change from start to start and reach the device
+    // by a copy from a host mirror written at issue: nothing to replay
+    if (req->Segmented()) return false;
     if (req->Compressed()) return true;  // single stream by construction
     if (gc.comms.size() > 1 && req->Chunks().size() > 1) return false;
     return true;
@@ -878,7 +919,7 @@ void IssueAll(CommRequest* req, GroupComms& gc, DeviceReqState& st, const IssueC
             if (compressed) {
                 // quantize -> dequantize keeps the quantized
                 // collective's semantics (and error feedback) at n=1
-                IssueCompressed(req, ce, static_cast<uint8_t*>(st.tmp_dev), sbase, rbase,
+                IssueCompressed(req, st, ce, static_cast<uint8_t*>(st.tmp_dev), sbase, rbase,
                                 s0, [](uint8_t*, uint8_t*) {});
             } else if (ce.sch.result.bytes && sbase != rbase) {
                 // NT copy kernel: measured faster than the blit path for
@@ -909,7 +950,7 @@ void IssueAll(CommRequest* req, GroupComms& gc, DeviceReqState& st, const IssueC
         if (compressed) {
             // quantize -> compressed-domain ring -> dequantize (driver
             // config 5: int8 allreduce / reduce-scatter of bf16/f32 grads)
-            IssueCompressed(req, ce, tbase, req->SendBuf(), req->RecvBuf(), strm_,
+            IssueCompressed(req, st, ce, tbase, req->SendBuf(), req->RecvBuf(), strm_,
                             [&](uint8_t* wire, uint8_t* scratch) { walk(wire, wire, scratch); });
             tmp_off += ce.qplan.bytes;
         } else if (ic.p2p || use_schedule) {
@@ -990,6 +1031,14 @@ void RecordCompletion(CommRequest* req, GroupComms& gc, DeviceReqState& st,
 }
 
 }  // namespace
+
+void DeviceCheckSegmentPointers(void* const* ptrs, size_t nseg) {
+    for (size_t j = 0; j < nseg; ++j)
+        MLSL_CHECK(ClassifyPtr(ptrs[j]) == BufClass::DEV,
+                   "start over a tensor list: tensor " + std::to_string(j) +
+                       " is not device memory (no staging is built for this request; "
+                       "move it to the device)");
+}
 
 double DeviceRequestCommMs(DeviceReqState& st) {
     if (!st.timed || !st.t0_event || st.events.empty()) return -1.0;

@@ -42,6 +42,9 @@ DeviceRuntime* CreateDeviceRuntime();
 // Request hooks (called from CommRequest/Engine).
 void DeviceSetupRequest(CommRequest* req, DeviceReqState& st);
 bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st);
+// Start of a request over a tensor list: throws, naming the first offender,
+// unless every pointer is device memory (nothing is staged for it).
+void DeviceCheckSegmentPointers(void* const* ptrs, size_t nseg);
 // hipEvent comm time of the last issued request (ms); -1 when not timed
 // (MLSL_STATS off) or not yet complete. Valid after completion.
 double DeviceRequestCommMs(DeviceReqState& st);

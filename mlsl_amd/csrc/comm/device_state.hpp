@@ -27,6 +27,13 @@ struct DeviceReqState {
     // Persistent device scratch (allocated at Setup in device mode).
     void* tmp_dev = nullptr;
     size_t tmp_bytes = 0;
+    // Requests over a tensor list: the device tables the gather and scatter
+    // kernels read. One HBM allocation, nseg + 1 prefix offsets (uploaded at
+    // Setup) then nseg pointers; the pointers change from start to start, so
+    // each issue writes them into the pinned mirror and copies them over on
+    // the request's stream, ahead of the prologue.
+    void* seg_dev = nullptr;
+    void** seg_ptrs_pin = nullptr;
     // Host-buffer staging (reference ReplaceIn/ReplaceOut,
     // src/comm_ep.cpp:363-566): user buffers that are not device memory are
     // staged through persistent HBM buffers around the collective. Pageable

@@ -268,6 +268,93 @@ void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t cou
     }
 }
 
+namespace {
+
+// Element idx of the concatenation -> its tensor: a cursor that walks the
+// prefix table either way, so the sequential passes of the codec cost one
+// step per boundary crossed.
+struct SegCursor {
+    const uint64_t* offs;
+    size_t nseg;
+    size_t s = 0;
+    // (tensor, element in it) of idx < offs[nseg]
+    size_t Seek(size_t idx) {
+        while (idx < offs[s]) --s;
+        while (s + 1 < nseg && idx >= offs[s + 1]) ++s;
+        return idx - offs[s];
+    }
+};
+
+void CheckSegTables(const void* ptrs, const uint64_t* offs, size_t nseg, size_t count,
+                    DataType dt, const char* where) {
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW(std::string(where) + " supports f32/bf16 only");
+    MLSL_CHECK(nseg >= 1, std::string(where) + " takes at least one segment");
+    MLSL_CHECK(ptrs != nullptr && offs != nullptr, std::string(where) + ": null segment table");
+    MLSL_CHECK(offs[0] == 0 && offs[nseg] == count,
+               std::string(where) + ": offsets do not run from 0 to count");
+    for (size_t j = 0; j < nseg; ++j)
+        MLSL_CHECK(offs[j + 1] > offs[j],
+                   std::string(where) + ": segment " + std::to_string(j) + " is empty");
+}
+
+}  // namespace
+
+void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                        void* err, void* wire, size_t count, size_t block, DataType dt,
+                        bool use_err) {
+    CheckQuantBlock(block, "HostQuantizeGather");
+    CheckSegTables(seg_ptrs, seg_offs, nseg, count, dt, "quantize-gather");
+    SegCursor cur{seg_offs, nseg};
+    // HostQuantize's two instantiations, reading through the cursor
+    if (dt == DataType::F32) {
+        float* e = static_cast<float*>(err);
+        auto in = [&](size_t i) {
+            const size_t k = cur.Seek(i);
+            return static_cast<const float*>(seg_ptrs[cur.s])[k];
+        };
+        QuantizeImpl([&](size_t i, bool ue) { return ue ? in(i) + e[i] : in(i); },
+                     [&](size_t i, float v) { e[i] = v; }, wire, count, block, use_err);
+    } else {
+        uint16_t* e = static_cast<uint16_t*>(err);
+        auto in = [&](size_t i) {
+            const size_t k = cur.Seek(i);
+            return Bf16F(static_cast<const uint16_t*>(seg_ptrs[cur.s])[k]);
+        };
+        QuantizeImpl([&](size_t i, bool ue) { return ue ? in(i) + Bf16F(e[i]) : in(i); },
+                     [&](size_t i, float v) { e[i] = F32B(v); }, wire, count, block, use_err);
+    }
+}
+
+void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64_t* seg_offs,
+                           size_t nseg, size_t count, size_t block, DataType dt,
+                           float post_scale, bool round_first) {
+    CheckQuantBlock(block, "HostDequantizeScatter");
+    const bool pre_round = round_first && dt == DataType::BF16;
+    CheckSegTables(seg_ptrs, seg_offs, nseg, count, dt, "dequantize-scatter");
+    SegCursor cur{seg_offs, nseg};
+    const size_t nblocks = (count + block - 1) / block;
+    const uint8_t* w = static_cast<const uint8_t*>(wire);
+    for (size_t b = 0; b < nblocks; ++b) {
+        const size_t base = b * block;
+        const size_t n = std::min(block, count - base);
+        const uint8_t* wb = w + b * (block + kWireHdr);
+        float scale;
+        std::memcpy(&scale, wb, 4);
+        const int8_t* payload = reinterpret_cast<const int8_t*>(wb + kWireHdr);
+        for (size_t i = 0; i < n; ++i) {
+            const size_t k = cur.Seek(base + i);
+            // two roundings to float, as the device kernel: never one product
+            // with scale * post_scale
+            float dq = payload[i] * scale;
+            if (pre_round) dq = Bf16F(F32B(dq));
+            const float v = dq * post_scale;
+            if (dt == DataType::F32) static_cast<float*>(seg_ptrs[cur.s])[k] = v;
+            else static_cast<uint16_t*>(seg_ptrs[cur.s])[k] = F32B(v);
+        }
+    }
+}
+
 const QuantPluginApi* LoadQuantPlugin(const QuantParams& qp) {
     if (qp.lib_path.empty()) return nullptr;
     static std::mutex mu;

@@ -52,6 +52,28 @@ void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
 void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t count,
                             size_t block, DataType dt, bool accumulate);
 
+// Prologue and finish of the quantized allreduce over a list of tensors, whose
+// concatenation V (count elements) is never materialised: tensor j holds
+// V[seg_offs[j], seg_offs[j + 1]), with nseg + 1 prefix offsets in elements
+// (seg_offs[0] == 0, seg_offs[nseg] == count, no empty tensor) and nseg
+// pointers aligned to the element size only.
+// Gather: wire, and the flat residual err of count elements when use_err, get
+// the bytes HostQuantize writes for V; the tensors are only read. Bit for bit
+// what LaunchQuantizeGather computes.
+void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                        void* err, void* wire, size_t count, size_t block, DataType dt,
+                        bool use_err);
+// Scatter: every element becomes (q * scale) * post_scale, both products
+// rounded to float and one final rounding for bf16; with post_scale == 1.0f
+// the bits of HostDequantize. Only the tensors are written. Bit for bit what
+// LaunchDequantizeScatter computes. round_first (bf16; nothing changes for
+// f32): q * scale is rounded to bf16 before it is scaled, the bits of
+// HostDequantize followed by a float multiplication of the stored elements;
+// the request's finish uses it.
+void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64_t* seg_offs,
+                           size_t nseg, size_t count, size_t block, DataType dt,
+                           float post_scale, bool round_first = false);
+
 // dlopen'd compression plugin (reference quant/quant.c ABI — Intel
 // DL-comp style). Loaded once per lib_path; used by the HOST compressed
 // path when QuantParams.lib_path is set. Signatures quant/quant.c:57-65.

@@ -60,6 +60,24 @@ void CommRequest::AddAllReduce(size_t count, ReduceOp op) {
     spec_.rop = op;
 }
 
+void CommRequest::AddAllReduceSegments(const std::vector<size_t>& counts, float post_scale) {
+    MLSL_CHECK(!counts.empty(),
+               "quantized all_reduce over a tensor list needs at least one tensor "
+               "(nseg == 0)");
+    std::vector<uint64_t> offs(counts.size() + 1, 0);
+    for (size_t j = 0; j < counts.size(); ++j) {
+        MLSL_CHECK(counts[j] > 0, "quantized all_reduce over a tensor list: tensor " +
+                                      std::to_string(j) + " has a zero count");
+        offs[j + 1] = offs[j] + counts[j];
+    }
+    MLSL_ADD_OP();
+    spec_.op = CollOp::ALLREDUCE;
+    spec_.count = static_cast<size_t>(offs.back());
+    spec_.rop = ReduceOp::SUM;
+    seg_offs_ = std::move(offs);
+    post_scale_ = post_scale;
+}
+
 void CommRequest::AddReduce(size_t count, ReduceOp op, int root) {
     MLSL_ADD_OP();
     spec_.op = CollOp::REDUCE;
@@ -470,7 +488,19 @@ void CommRequest::BuildChunks() {
 
 void CommRequest::Setup() {
     MLSL_CHECK(has_op_, "Setup() before describing the op");
+    if (Segmented()) {
+        // never an exact allreduce of the list behind the caller's back
+        MLSL_CHECK(dtype_ == DataType::F32 || dtype_ == DataType::BF16,
+                   "quantized all_reduce over a tensor list supports f32/bf16 only");
+        MLSL_CHECK(comp_ == Compression::QUANT_INT8,
+                   "all_reduce over a tensor list exists quantized only "
+                   "(SetCompression(QUANT_INT8))");
+    }
     BuildChunks();
+    // after BuildChunks, whose two-shot refusals come first with their own text
+    MLSL_CHECK(!Segmented() || plugin_ == nullptr,
+               "quantized all_reduce over a tensor list cannot run with a compression "
+               "plugin (the plugin ABI quantizes one flat buffer); unset lib_path");
     Context& ctx = Context::Get();
     if (ctx.DeviceMode()) {
         dev_ = std::make_unique<DeviceState>();
@@ -497,6 +527,34 @@ uint64_t CommRequest::MakeTag(size_t chunk, int phase) const {
 }
 
 void CommRequest::Start(const void* sbuf, void* rbuf) {
+    MLSL_CHECK(!Segmented(),
+               "this request runs over a tensor list: start it with StartSegments "
+               "(mlsl_request_start_segments)");
+    StartCommon(sbuf, rbuf);
+}
+
+void CommRequest::StartSegments(void* const* ptrs, size_t nseg) {
+    MLSL_CHECK(Segmented(), "StartSegments on a request that was not described over a "
+                            "tensor list");
+    MLSL_CHECK(setup_done_, "Start() before Setup()");
+    ReqState st = state_.load(std::memory_order_acquire);
+    MLSL_CHECK(st == ReqState::IDLE || st == ReqState::DONE,
+               "Start() while request in flight");
+    const size_t want = seg_offs_.size() - 1;
+    MLSL_CHECK(nseg == want, "start with " + std::to_string(nseg) +
+                                 " tensors on a request created over " +
+                                 std::to_string(want) + " (nseg differs from creation)");
+    MLSL_CHECK(ptrs != nullptr, "start over a tensor list: null pointer list");
+    for (size_t j = 0; j < nseg; ++j)
+        MLSL_CHECK(ptrs[j] != nullptr,
+                   "start over a tensor list: tensor " + std::to_string(j) + " is null");
+    // refused before anything of the last start is overwritten
+    if (Context::Get().DeviceMode()) DeviceCheckSegmentPointers(ptrs, nseg);
+    seg_ptrs_.assign(ptrs, ptrs + nseg);
+    StartCommon(nullptr, nullptr);
+}
+
+void CommRequest::StartCommon(const void* sbuf, void* rbuf) {
     MLSL_CHECK(setup_done_, "Start() before Setup()");
     ReqState st = state_.load(std::memory_order_acquire);
     MLSL_CHECK(st == ReqState::IDLE || st == ReqState::DONE,
@@ -519,7 +577,7 @@ void CommRequest::Start(const void* sbuf, void* rbuf) {
     error_.clear();
 
     Context& ctx = Context::Get();
-    if (GlobalConfig().check_pointers) {
+    if (GlobalConfig().check_pointers && !Segmented()) {
         // Pointer checker (reference src/pointer_checker.*): every buffer
         // handed to a collective must be a known registered allocation.
         const size_t bytes = MessageBytes();
@@ -628,8 +686,15 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
         };
         if (compressed && !ce.prologue_done) {
             // quantize user send (+ residual, where the plan has one) into
-            // the wire
-            for (size_t j = 0; j < qp.nseg; ++j) {
+            // the wire; over a tensor list (one plan segment) straight from the
+            // tensors
+            if (Segmented())
+                HostQuantizeGather(seg_ptrs_.data(), seg_offs_.data(), seg_ptrs_.size(),
+                                   qp.residual ? wire + qp.err_off : nullptr,
+                                   wire + qp.send_seg * qp.seg_wire, qp.count, qp.block,
+                                   dtype_, qp.residual);
+            const size_t flat_segs = Segmented() ? 0 : qp.nseg;
+            for (size_t j = 0; j < flat_segs; ++j) {
                 const uint8_t* seg = sbase + j * qp.seg_bytes;
                 uint8_t* seg_err =
                     qp.residual ? wire + qp.err_off + j * qp.seg_bytes : nullptr;
@@ -749,7 +814,14 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                                                     qp.block, dtype_);
                                 break;
                             case QuantFinish::DEQUANT:
-                                HostDequantize(wires[0], rbase, qp.count, qp.block, dtype_);
+                                if (Segmented())
+                                    HostDequantizeScatter(wires[0], seg_ptrs_.data(),
+                                                          seg_offs_.data(), seg_ptrs_.size(),
+                                                          qp.count, qp.block, dtype_,
+                                                          post_scale_,
+                                                          /*round_first=*/true);
+                                else
+                                    HostDequantize(wires[0], rbase, qp.count, qp.block, dtype_);
                                 break;
                             case QuantFinish::SCATTER:
                                 HostDequantizeSegments(wires[0], qp.out_segs, rbase, qp.count,

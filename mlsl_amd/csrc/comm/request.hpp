@@ -94,6 +94,14 @@ class CommRequest {
 
     // ---- description (CommDesc analog) ----
     void AddAllReduce(size_t count, ReduceOp op);
+    // The quantized allreduce (SUM) over a list of tensors of counts[j] >= 1
+    // elements, in place: an ALLREDUCE of their concatenation, which is never
+    // built. Only the quantize prologue and the dequantize finish differ from
+    // AddAllReduce + SetCompression: they read and write the tensors where
+    // they lie (quant.hpp, HostQuantizeGather / HostDequantizeScatter), and
+    // the finish multiplies by post_scale. Needs SetCompression(QUANT_INT8)
+    // on f32/bf16 without a plugin, or Setup() fails; runs with StartSegments.
+    void AddAllReduceSegments(const std::vector<size_t>& counts, float post_scale);
     void AddReduce(size_t count, ReduceOp op, int root);
     void AddReduceScatter(size_t recv_count, ReduceOp op);
     void AddAllGather(size_t send_count);
@@ -141,6 +149,10 @@ class CommRequest {
     // ---- lifecycle ----
     void Setup();                         // compile schedules, size scratch
     void Start(const void* sbuf, void* rbuf);
+    // Start of an AddAllReduceSegments request: the nseg tensor pointers of
+    // this start (they may differ from the last one's). In device mode every
+    // one must be device memory: nothing is staged for such a request.
+    void StartSegments(void* const* ptrs, size_t nseg);
     void* Wait();                         // returns result pointer
     bool Test();                          // true when complete
     size_t GetTmpBytes() const { return total_tmp_bytes_; }
@@ -177,10 +189,17 @@ class CommRequest {
         dev_sbuf_ = s;
         dev_rbuf_ = r;
     }
+    // AddAllReduceSegments requests: nseg + 1 prefix offsets in elements
+    // (fixed at description), this start's nseg pointers, the finish's factor.
+    bool Segmented() const { return !seg_offs_.empty(); }
+    const std::vector<uint64_t>& SegOffs() const { return seg_offs_; }
+    const std::vector<void*>& SegPtrs() const { return seg_ptrs_; }
+    float PostScale() const { return post_scale_; }
 
   private:
     friend class Engine;
     void BuildChunks();
+    void StartCommon(const void* sbuf, void* rbuf);
     uint64_t MakeTag(size_t chunk, int phase) const;
     uint64_t PairTag(uint32_t seq) const;
 
@@ -197,6 +216,9 @@ class CommRequest {
     bool qag_accumulate_ = false;
     QuantArAlgo qar_algo_ = QuantArAlgo::RING;   // meaningful once qar_named_
     bool qar_named_ = false;   // false: MLSL_QUANT_AR_ALGO decides at Setup()
+    std::vector<uint64_t> seg_offs_;   // empty unless AddAllReduceSegments
+    std::vector<void*> seg_ptrs_;      // per StartSegments
+    float post_scale_ = 1.0f;
 
     std::vector<ChunkExec> chunks_;
     size_t total_tmp_bytes_ = 0;

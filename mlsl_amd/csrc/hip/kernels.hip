@@ -1530,6 +1530,290 @@ void LaunchDequantizeSegments(const void* wire, size_t nseg, void* out, size_t c
     HIP_CHECK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------
+// Quantize from, and dequantize into, a list of tensors: the prologue and the
+// finish of the allreduce over a list (DDP gradient buckets). The
+// concatenation V of the nseg tensors is never materialised: the wire's block
+// grid runs over V's element index, tensor j holds V[offs[j], offs[j + 1]),
+// and both tables (nseg + 1 prefix offsets, nseg pointers) are read from
+// device memory. A wave finds the tensor of its block's first element once,
+// by a wave-uniform bisection of the offsets. A block that lies inside one
+// tensor, at a 16-byte aligned address, then runs the flat kernels' 4-wide
+// loop on that tensor (a whole 256-block of the gather: four elements per
+// lane, read once and kept in registers); any other block goes element by
+// element, every lane walking forward through the table from the block's
+// first tensor. The wave keeps its tensor from one block to its next.
+//
+// Traffic per element is the flat kernels': sizeof(T) in (twice that with a
+// residual, which is also written) and 1 wire byte out, or 1 wire byte in and
+// sizeof(T) out; plus one bisection of 8-byte offsets per block.
+
+namespace {
+
+struct SegTable {
+    const uint64_t* offs;   // nseg + 1 prefix offsets in elements; offs[0] == 0
+    uint32_t nseg;
+};
+
+// Largest j with offs[j] <= idx, for idx < offs[nseg], given offs[lo] <= idx.
+__device__ __forceinline__ uint32_t SegOf(const SegTable& t, uint64_t idx, uint32_t lo) {
+    uint32_t hi = t.nseg;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (t.offs[mid] <= idx) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The tensor of a wave's current block, kept across its grid-stride trips: a
+// wave's blocks ascend, so a block inside the tensor of the last one costs no
+// table read, and any other is found by a bisection that starts there.
+template <typename T>
+struct SegCursor {
+    uint32_t seg = 0;
+    uint64_t lo = 0, hi = 0;   // the tensor holds V[lo, hi); hi == 0: none yet
+    T* ptr = nullptr;
+    template <typename P>
+    __device__ __forceinline__ void Seek(const SegTable& t, P ptrs, uint64_t base) {
+        if (base < hi) return;
+        seg = SegOf(t, base, seg);
+        lo = t.offs[seg];
+        hi = t.offs[seg + 1];
+        ptr = ptrs[seg];
+    }
+};
+
+// f(i, p) for the elements i = lane, lane + 64, ... < n of the block that
+// starts at V[base], p pointing at element base + i in its tensor. `c` is at
+// the tensor of V[base]; the lane's own cursor only ever moves forward.
+template <typename T, typename P, typename F>
+__device__ __forceinline__ void ForEachSegElem(const SegTable& t, P ptrs,
+                                               const SegCursor<T>& c, uint64_t base, size_t n,
+                                               int lane, F f) {
+    uint32_t s = c.seg;
+    uint64_t lo = c.lo, hi = c.hi;
+    T* p = c.ptr;
+    for (size_t i = lane; i < n; i += 64) {
+        const uint64_t e = base + i;
+        if (e >= hi) {
+            // the table's last entry bounds the walk whatever `count` says
+            while (e >= hi && s + 1 < t.nseg) hi = t.offs[++s + 1];
+            lo = t.offs[s];
+            p = ptrs[s];
+        }
+        f(i, p + (e - lo));
+    }
+}
+
+template <typename T, bool USE_ERR>
+__global__ void QuantizeGatherKernel(const T* const* __restrict__ ptrs, SegTable tab,
+                                     T* __restrict__ err, uint8_t* __restrict__ wire,
+                                     size_t count, size_t block_elems) {
+    using V4 = std::conditional_t<sizeof(T) == 4, float4_ev, ushort4_t>;
+    SegCursor<const T> cur;
+    // whole 256-blocks may stay in registers when err takes vector accesses
+    const bool regs = block_elems == kFastBlock &&
+                      (!USE_ERR || (reinterpret_cast<uintptr_t>(err) & 15) == 0);
+    ForEachWaveBlock((count + block_elems - 1) / block_elems, [&](size_t vblk, int lane) {
+        // uniform across the wave: the bisection and the table reads stay in
+        // scalar registers
+        const size_t blk = (static_cast<size_t>(__builtin_amdgcn_readfirstlane(
+                                static_cast<uint32_t>(vblk >> 32))) << 32) |
+                           __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vblk));
+        const size_t base = blk * block_elems;
+        const size_t n = min(block_elems, count - base);
+        uint8_t* wblock = wire + blk * (block_elems + kWireHdr);
+        int8_t* payload = reinterpret_cast<int8_t*>(wblock + kWireHdr);
+        cur.Seek(tab, ptrs, base);
+        const T* in = cur.ptr + (base - cur.lo);   // V[base], if the block is whole
+        const bool whole = base + n <= cur.hi;
+        const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+
+        if (whole && aligned && regs && n == kFastBlock) {
+            // four consecutive elements per lane, read once and kept in
+            // registers: QuantizeKernel's arithmetic per element
+            const V4 a = *reinterpret_cast<const V4*>(in + lane * 4);
+            V4 e{};
+            if (USE_ERR) e = *reinterpret_cast<const V4*>(err + base + lane * 4);
+            float v[4];
+            float m = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] = Decode<T>(a[j]);
+                if (USE_ERR) v[j] += Decode<T>(e[j]);
+                m = fmaxf(m, fabsf(v[j]));
+            }
+            const float scale = QScale(WaveMax(m));
+            if (lane == 0) WriteWireHeader(wblock, scale);
+            const float inv = 1.f / scale;
+            uint32_t packed = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float q = QRound(v[j], inv);
+                packed |= QPack(q, j);
+                if (USE_ERR) e[j] = Encode<T>(v[j] - q * scale);
+            }
+            QStore<4>(payload, lane * 4, packed);
+            if (USE_ERR) StoreVec<false>(e, err + base + lane * 4);
+        } else if (whole && aligned) {
+            // QuantizeKernel's block body on this tensor
+            auto value = [&](size_t i) {
+                float v = Decode(in[i]);
+                if (USE_ERR) v += Decode(err[base + i]);
+                return v;
+            };
+            float m = 0.f;
+            ForEachBlockElem(n, true, lane, [&](size_t i, auto w) {
+#pragma unroll
+                for (int j = 0; j < decltype(w)::value; ++j)
+                    m = fmaxf(m, fabsf(value(i + j)));
+            });
+            const float scale = QScale(WaveMax(m));
+            if (lane == 0) WriteWireHeader(wblock, scale);
+            const float inv = 1.f / scale;
+            ForEachBlockElem(n, true, lane, [&](size_t i, auto w) {
+                constexpr int W = decltype(w)::value;
+                uint32_t packed = 0;
+#pragma unroll
+                for (int j = 0; j < W; ++j) {
+                    const float v = value(i + j);
+                    const float q = QRound(v, inv);
+                    packed |= QPack(q, j);
+                    if (USE_ERR) err[base + i + j] = Encode<T>(v - q * scale);
+                }
+                QStore<W>(payload, i, packed);
+            });
+        } else {
+            auto value = [&](size_t i, const T* p) {
+                float v = Decode(*p);
+                if (USE_ERR) v += Decode(err[base + i]);
+                return v;
+            };
+            float m = 0.f;
+            ForEachSegElem<const T>(tab, ptrs, cur, base, n, lane, [&](size_t i, const T* p) {
+                m = fmaxf(m, fabsf(value(i, p)));
+            });
+            const float scale = QScale(WaveMax(m));
+            if (lane == 0) WriteWireHeader(wblock, scale);
+            const float inv = 1.f / scale;
+            ForEachSegElem<const T>(tab, ptrs, cur, base, n, lane, [&](size_t i, const T* p) {
+                const float v = value(i, p);
+                const float q = QRound(v, inv);
+                payload[i] = static_cast<int8_t>(q);
+                if (USE_ERR) err[base + i] = Encode<T>(v - q * scale);
+            });
+        }
+        for (size_t i = n + lane; i < block_elems; i += 64) payload[i] = 0;
+    });
+}
+
+// ROUND_FIRST (bf16 only; f32 would not change): q * scale is rounded into T
+// before it is scaled, which is what LaunchDequantize followed by a
+// multiplication of the stored elements gives.
+template <typename T, bool ROUND_FIRST>
+__global__ void DequantizeScatterKernel(const uint8_t* __restrict__ wire, T* const* ptrs,
+                                        SegTable tab, size_t count, size_t block_elems,
+                                        float post_scale) {
+    SegCursor<T> cur;
+    ForEachWaveBlock((count + block_elems - 1) / block_elems, [&](size_t vblk, int lane) {
+        const size_t blk = (static_cast<size_t>(__builtin_amdgcn_readfirstlane(
+                                static_cast<uint32_t>(vblk >> 32))) << 32) |
+                           __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vblk));
+        const size_t base = blk * block_elems;
+        const size_t n = min(block_elems, count - base);
+        const uint8_t* wblock = wire + blk * (block_elems + kWireHdr);
+        const float scale = WireScale(wblock);
+        const int8_t* payload = reinterpret_cast<const int8_t*>(wblock + kWireHdr);
+        cur.Seek(tab, ptrs, base);
+        T* out = cur.ptr + (base - cur.lo);
+        const bool whole = base + n <= cur.hi;
+        // two roundings to float, then one into T: never (scale * post_scale)
+        auto elem = [&](int q) {
+            float dq = q * scale;
+            if constexpr (ROUND_FIRST) dq = Decode<T>(Encode<T>(dq));
+            return Encode<T>(dq * post_scale);
+        };
+
+        if (whole && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+            ForEachBlockElem(n, true, lane, [&](size_t i, auto w) {
+                constexpr int W = decltype(w)::value;
+                const int32_t packed = QLoad<W>(payload, i);
+                if constexpr (W == 4) {
+                    using V = std::conditional_t<sizeof(T) == 4, float4_ev, ushort4_t>;
+                    V v;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = elem(QUnpack(packed, j));
+                    StoreVec<false>(v, out + i);
+                } else {
+                    out[i] = elem(QUnpack(packed, 0));
+                }
+            });
+        } else {
+            ForEachSegElem<T>(tab, ptrs, cur, base, n, lane,
+                              [&](size_t i, T* p) { *p = elem(payload[i]); });
+        }
+    });
+}
+
+void CheckSegArgs(const void* ptrs, const void* offs, size_t nseg, size_t count, DataType dt,
+                  const char* where) {
+    if (dt != DataType::F32 && dt != DataType::BF16)
+        MLSL_THROW(std::string(where) + " supports f32/bf16 only");
+    MLSL_CHECK(nseg >= 1 && nseg <= 0xffffffffull && count >= nseg,
+               std::string(where) + " takes at least one segment of at least one element");
+    MLSL_CHECK(ptrs != nullptr && offs != nullptr,
+               std::string(where) + ": null segment table");
+}
+
+}  // namespace
+
+void LaunchQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                          void* err, void* wire, size_t count, size_t block_elems,
+                          DataType dt, bool use_err, hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchQuantizeGather");
+    CheckSegArgs(seg_ptrs, seg_offs, nseg, count, dt, "quantize-gather");
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const dim3 grid = WaveGrid(NumBlocks(count, block_elems));
+    uint8_t* w = static_cast<uint8_t*>(wire);
+    DispatchBool(use_err, [&](auto ue) {
+        constexpr bool UE = decltype(ue)::value;
+        if (dt == DataType::F32)
+            QuantizeGatherKernel<float, UE><<<grid, dim3(kBlock), 0, stream>>>(
+                reinterpret_cast<const float* const*>(seg_ptrs), tab,
+                static_cast<float*>(err), w, count, block_elems);
+        else
+            QuantizeGatherKernel<unsigned short, UE><<<grid, dim3(kBlock), 0, stream>>>(
+                reinterpret_cast<const unsigned short* const*>(seg_ptrs), tab,
+                static_cast<unsigned short*>(err), w, count, block_elems);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+void LaunchDequantizeScatter(const void* wire, void* const* seg_ptrs,
+                             const uint64_t* seg_offs, size_t nseg, size_t count,
+                             size_t block_elems, DataType dt, float post_scale,
+                             bool round_first, hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchDequantizeScatter");
+    CheckSegArgs(seg_ptrs, seg_offs, nseg, count, dt, "dequantize-scatter");
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const dim3 grid = WaveGrid(NumBlocks(count, block_elems));
+    const uint8_t* w = static_cast<const uint8_t*>(wire);
+    if (dt == DataType::F32) {
+        // q * scale already is an f32: rounding it first changes nothing
+        DequantizeScatterKernel<float, false><<<grid, dim3(kBlock), 0, stream>>>(
+            w, reinterpret_cast<float* const*>(seg_ptrs), tab, count, block_elems, post_scale);
+    } else {
+        DispatchBool(round_first, [&](auto rf) {
+            DequantizeScatterKernel<unsigned short, decltype(rf)::value>
+                <<<grid, dim3(kBlock), 0, stream>>>(
+                    w, reinterpret_cast<unsigned short* const*>(seg_ptrs), tab, count,
+                    block_elems, post_scale);
+        });
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
 // --- IPC p2p transport (comm/p2p_transport.cpp) ---
 // Mailboxes are monotonically increasing u64 sequence counters in the
 // receiver's HBM window; the writer is a remote process on the same or a

@@ -101,6 +101,33 @@ void LaunchDequantizeSegments(const void* wire, size_t nseg, void* out, size_t c
                               size_t block_elems, DataType dt, bool accumulate,
                               hipStream_t stream);
 
+// Prologue and finish of the quantized allreduce over a list of tensors. The
+// concatenation V of the nseg tensors (count elements in all, fp32/bf16) is
+// never materialised: tensor j holds V[seg_offs[j], seg_offs[j + 1]). Both
+// tables are DEVICE memory: nseg + 1 prefix offsets in elements (seg_offs[0]
+// == 0, seg_offs[nseg] == count, every tensor at least one element) and nseg
+// tensor pointers, each aligned to the element size only. Boundaries may fall
+// anywhere inside a wire block.
+// Gather: `wire`, and `err` (one flat residual of count elements in V's
+// order) when use_err, get the bytes LaunchQuantize writes for V; the tensors
+// are only read.
+void LaunchQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                          void* err, void* wire, size_t count, size_t block_elems,
+                          DataType dt, bool use_err, hipStream_t stream);
+// Scatter: every element becomes Encode((q * scale) * post_scale), both
+// products rounded to float and one final rounding for bf16: with post_scale
+// == 1.0f the bits of LaunchDequantize. The wire is only read and no byte
+// outside the tensors is written.
+// round_first (bf16; nothing changes for fp32): q * scale is rounded to bf16
+// before the scaling, Encode(Decode(Encode(q * scale)) * post_scale): the bits
+// of LaunchDequantize followed by a float multiplication of the stored
+// elements. The request uses it, so that a list request and a flat request
+// plus a scaling of its result agree bit for bit whatever post_scale is.
+void LaunchDequantizeScatter(const void* wire, void* const* seg_ptrs,
+                             const uint64_t* seg_offs, size_t nseg, size_t count,
+                             size_t block_elems, DataType dt, float post_scale,
+                             bool round_first, hipStream_t stream);
+
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,
 // the consumer does the copy — tests/examples/mlsl_test/mlsl_test.cpp:214-254.

@@ -118,6 +118,30 @@ int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
                                               mlsl_data_type dt, mlsl_reduction op,
                                               mlsl_group g, mlsl_quant_ar_algo algo,
                                               mlsl_request* out);
+/* The int8-quantized allreduce (a sum) over a LIST of nseg tensors of
+ * counts[j] >= 1 elements each, in place: it is the quantized allreduce of
+ * their concatenation, which is never built. The quantize prologue reads the
+ * tensors where they lie, and the finish writes post_scale x the allreduced
+ * values of its own range back into tensor j: element = (q * scale) *
+ * post_scale, both products rounded to float (two roundings, so 1/N here is
+ * not the bits of a division afterwards). Bit for bit this is the flat
+ * quantized allreduce's result times post_scale in float, rounded to dt: for
+ * bf16, q * scale is rounded to bf16 before it is scaled. The residual
+ * is one flat buffer of sum(counts) elements kept across starts. algo: -1
+ * takes MLSL_QUANT_AR_ALGO, 0 the ring, 1 two-shot (limits as above).
+ * The pointers are given at every start (mlsl_request_start_segments) and may
+ * change between starts; each needs the element's alignment only. Overlapping
+ * tensors are the caller's error and are not checked. In device mode every
+ * pointer must be device memory: nothing is staged. wait/test/destroy as for
+ * any request; mlsl_request_start on such a request fails.
+ * Fails at creation unless dt is f32 or bf16, for nseg == 0 or a zero count,
+ * and with a compression plugin (lib_path), whose ABI quantizes one flat
+ * buffer. */
+int mlsl_persistent_all_reduce_quantized_segments(mlsl_distribution d, const size_t* counts,
+                                                  size_t nseg, mlsl_data_type dt,
+                                                  mlsl_group g, int algo, float post_scale,
+                                                  mlsl_request* out);
+int mlsl_request_start_segments(mlsl_request req, void* const* ptrs, size_t nseg);
 int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
                                    mlsl_data_type dt, mlsl_reduction op, mlsl_group g,
                                    mlsl_request* out);

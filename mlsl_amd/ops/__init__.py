@@ -53,6 +53,27 @@ def _lib():
         L.mlsl_host_dequantize_segments.argtypes = L.mlsl_hip_dequantize_segments.argtypes
         L.mlsl_hip_dequantize_segments.restype = c.c_int
         L.mlsl_host_dequantize_segments.restype = c.c_int
+        L.mlsl_hip_quantize_gather.argtypes = [c.POINTER(c.c_void_p),
+                                               c.POINTER(c.c_size_t), c.c_size_t,
+                                               c.c_void_p, c.c_void_p, c.c_size_t,
+                                               c.c_int, c.c_int]
+        L.mlsl_host_quantize_gather.argtypes = L.mlsl_hip_quantize_gather.argtypes
+        L.mlsl_hip_dequantize_scatter.argtypes = [c.c_void_p, c.POINTER(c.c_void_p),
+                                                  c.POINTER(c.c_size_t), c.c_size_t,
+                                                  c.c_size_t, c.c_int, c.c_float,
+                                                  c.c_int]
+        L.mlsl_host_dequantize_scatter.argtypes = L.mlsl_hip_dequantize_scatter.argtypes
+        L.mlsl_hip_quantize_gather_tables.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t,
+                                                      c.c_void_p, c.c_void_p, c.c_size_t,
+                                                      c.c_size_t, c.c_int, c.c_int]
+        L.mlsl_hip_dequantize_scatter_tables.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p,
+                                                         c.c_size_t, c.c_size_t, c.c_size_t,
+                                                         c.c_int, c.c_float, c.c_int]
+        L.mlsl_hip_quantize_gather_tables.restype = c.c_int
+        L.mlsl_hip_dequantize_scatter_tables.restype = c.c_int
+        for n in ("mlsl_hip_quantize_gather", "mlsl_host_quantize_gather",
+                  "mlsl_hip_dequantize_scatter", "mlsl_host_dequantize_scatter"):
+            getattr(L, n).restype = c.c_int
         L.mlsl_host_quantize.argtypes = L.mlsl_hip_quantize.argtypes
         L.mlsl_host_dequantize.argtypes = L.mlsl_hip_dequantize.argtypes
         L.mlsl_host_quant_accum.argtypes = L.mlsl_hip_quant_accum.argtypes
@@ -218,7 +239,122 @@ def dequantize_segments(wire, out, count, nseg, block=256, dtype=None, accumulat
                                               1 if accumulate else 0))
 
 
+def _seg_tables(tensors, counts, dtype):
+    """(pointer array, count array, nseg, total, dtype name) of a list of
+    tensors: device tensors, raw pointers or anything _as_ptr_dtype takes."""
+    if len(tensors) != len(counts):
+        raise ValueError(f"{len(tensors)} tensors but {len(counts)} counts")
+    if not counts:
+        raise ValueError("the tensor list is empty: at least one segment is needed")
+    for j, n in enumerate(counts):
+        if int(n) < 1:
+            raise ValueError(f"counts[{j}] = {n}: every segment needs at least one element")
+    pd = [_as_ptr_dtype(t) for t in tensors]
+    ptrs = (ctypes.c_void_p * len(pd))(*[p.value for p, _ in pd])
+    return (ptrs, (ctypes.c_size_t * len(counts))(*[int(n) for n in counts]), len(counts),
+            sum(int(n) for n in counts), dtype or pd[0][1])
+
+
+def quantize_gather(tensors, counts, wire, err=None, block=256, dtype=None):
+    """`quantize` of the concatenation of `tensors` (counts[j] elements each,
+    f32/bf16) without materialising it: `wire`, and the flat residual `err` of
+    sum(counts) elements if given, get exactly the bytes `quantize` writes for
+    torch.cat(tensors). The tensors are only read; their addresses need the
+    element's alignment only, and boundaries fall anywhere in a wire block.
+    The segment tables are uploaded here, once per call."""
+    _check_block(block)
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather(ptrs, cnts, nseg, ep, wp, block, DTYPE[dt],
+                                          1 if err is not None else 0))
+
+
+def dequantize_scatter(wire, tensors, counts, block=256, dtype=None, post_scale=1.0,
+                       round_first=False):
+    """`dequantize` of `wire` into the list `tensors`, scaled: element i of
+    tensor j becomes (q * scale) * post_scale, both products rounded to
+    float32 (two roundings, never one product with scale * post_scale) and
+    bf16 rounded once more. post_scale=1.0 gives `dequantize`'s bits. The wire
+    is only read and nothing outside the tensors is written.
+    round_first=True (bf16; f32 does not change) rounds q * scale to bf16
+    before it is scaled: the bits of `dequantize` followed by a float32
+    multiplication of the stored elements, which is what the request over a
+    tensor list (SegmentedAllReduce) computes."""
+    _check_block(block)
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    wp, _ = _as_ptr_dtype(wire)
+    check(_lib().mlsl_hip_dequantize_scatter(wp, ptrs, cnts, nseg, block, DTYPE[dt],
+                                             post_scale, 1 if round_first else 0))
+
+
+def quantize_gather_tables(dev_ptrs, dev_offs, nseg, count, wire, err=None, block=256,
+                           dtype="f32"):
+    """`quantize_gather` over tables the caller keeps in DEVICE memory, as a
+    request does: dev_offs holds nseg + 1 prefix offsets (64-bit, from 0 to
+    count), dev_ptrs the nseg tensor addresses (64-bit). Nothing is uploaded
+    and nothing about the tables can be checked here."""
+    _check_block(block)
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    fp, _ = _as_ptr_dtype(dev_offs)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather_tables(pp, fp, nseg, ep, wp, count, block,
+                                                 DTYPE[dtype], 1 if err is not None else 0))
+
+
+def dequantize_scatter_tables(wire, dev_ptrs, dev_offs, nseg, count, block=256, dtype="f32",
+                              post_scale=1.0, round_first=False):
+    """`dequantize_scatter` over tables in DEVICE memory; see
+    `quantize_gather_tables`."""
+    _check_block(block)
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    fp, _ = _as_ptr_dtype(dev_offs)
+    wp, _ = _as_ptr_dtype(wire)
+    check(_lib().mlsl_hip_dequantize_scatter_tables(wp, pp, fp, nseg, count, block,
+                                                    DTYPE[dtype], post_scale,
+                                                    1 if round_first else 0))
+
+
 _ELEM_BYTES = {"f32": 4, "bf16": 2}
+
+
+def _host_seg_tables(arrays, counts, dtype, what):
+    if dtype not in _ELEM_BYTES:
+        raise ValueError(f"dtype {dtype!r}: the list codec supports f32/bf16 only")
+    if len(arrays) != len(counts):
+        raise ValueError(f"{len(arrays)} {what} but {len(counts)} counts")
+    if not counts:
+        raise ValueError("the tensor list is empty: at least one segment is needed")
+    for j, n in enumerate(counts):
+        if int(n) < 1:
+            raise ValueError(f"counts[{j}] = {n}: every segment needs at least one element")
+    eb = _ELEM_BYTES[dtype]
+    ptrs = (ctypes.c_void_p * len(arrays))(
+        *[_host_buf(a, int(n) * eb, f"{what}[{j}]").value
+          for j, (a, n) in enumerate(zip(arrays, counts))])
+    return (ptrs, (ctypes.c_size_t * len(counts))(*[int(n) for n in counts]), len(counts),
+            sum(int(n) for n in counts))
+
+
+def host_quantize_gather(arrays, counts, wire, err=None, block=256, dtype="f32"):
+    """Host twin of `quantize_gather` on numpy arrays: the same bits."""
+    _check_block(block)
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays")
+    wp = _host_buf(wire, wire_bytes(total, block), "wire")
+    ep = None if err is None else _host_buf(err, total * _ELEM_BYTES[dtype], "err")
+    check(_lib().mlsl_host_quantize_gather(ptrs, cnts, nseg, ep, wp, block, DTYPE[dtype],
+                                           1 if err is not None else 0))
+
+
+def host_dequantize_scatter(wire, arrays, counts, block=256, dtype="f32", post_scale=1.0,
+                            round_first=False):
+    """Host twin of `dequantize_scatter` on numpy arrays: the same bits."""
+    _check_block(block)
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays")
+    wp = _host_buf(wire, wire_bytes(total, block), "wire")
+    check(_lib().mlsl_host_dequantize_scatter(wp, ptrs, cnts, nseg, block, DTYPE[dtype],
+                                              post_scale, 1 if round_first else 0))
 
 
 def _host_buf(arr, need_bytes, what):

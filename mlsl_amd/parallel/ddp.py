@@ -15,6 +15,15 @@ Usage (one process per GPU):
 Gradients are bucketed (default 25 MiB) and allreduced non-blocking as
 buckets fill during backward — the reference's Backward2/Update overlap
 split, driven from torch autograd hooks.
+
+With compression="int8" every f32 or bf16 bucket is one
+mx.SegmentedAllReduce: the int8 wire's quantize pass reads the gradients
+where they lie and its dequantize pass writes the averaged values back into
+them, so there is no torch.cat, no divide and no copy-back, and
+finish_gradients() only waits. The average is (q * scale) * (1/world), two
+float32 roundings: the bits of a flat quantized allreduce of the bucket
+multiplied by float32(1/world). Buckets of any other dtype keep the exact path. Call
+close() to release the requests.
 """
 import torch
 
@@ -23,7 +32,12 @@ import mlsl_amd as mx
 
 class DistributedData:
     def __init__(self, module, dist=None, bucket_mb=25, group="data",
-                 average=True):
+                 average=True, compression=None, ar_algo=None):
+        if compression not in (None, "int8"):
+            raise ValueError(f"compression={compression!r}: expected None or 'int8'")
+        if ar_algo is not None and compression is None:
+            raise ValueError("ar_algo= selects the quantized all_reduce's algorithm: "
+                             "it needs compression='int8'")
         self.module = module
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
         self.group = group
@@ -70,6 +84,16 @@ class DistributedData:
         self._pending = [0] * len(self._buckets)
         self._reqs = [None] * len(self._buckets)
         self._flat = [None] * len(self._buckets)
+        # compression="int8": one request over the bucket's gradient list per
+        # f32/bf16 bucket; None marks a bucket on the exact path
+        self._seg = [None] * len(self._buckets)
+        if compression == "int8" and self.world > 1:
+            for bi, ps in enumerate(self._buckets):
+                if ps[0].dtype in (torch.float32, torch.bfloat16):
+                    self._seg[bi] = mx.SegmentedAllReduce(
+                        self.dist, [q.numel() for q in ps], dtype=_dt(ps[0]),
+                        group=group, ar_algo=ar_algo,
+                        post_scale=1.0 / self.world if average else 1.0)
 
         for p in self._params:
             p.register_post_accumulate_grad_hook(self._hook)
@@ -86,6 +110,17 @@ class DistributedData:
         self._pending[bi] -= 1
         if self._pending[bi] == 0:
             ps = self._buckets[bi]
+            if self._seg[bi] is not None:
+                grads = [q.grad for q in ps]
+                for q, g in zip(ps, grads):
+                    if not g.is_contiguous():
+                        raise ValueError(
+                            "compression='int8' reduces gradients in place and needs "
+                            f"them contiguous: the gradient of a parameter of shape "
+                            f"{tuple(q.shape)} has strides {g.stride()}")
+                self._seg[bi].start(grads)
+                self._reqs[bi] = self._seg[bi]
+                return
             flat = torch.cat([q.grad.detach().reshape(-1) for q in ps])
             self._flat[bi] = flat
             self._reqs[bi] = self.dist.all_reduce(flat, flat, flat.numel(),
@@ -99,6 +134,11 @@ class DistributedData:
         for bi, ps in enumerate(self._buckets):
             if self._reqs[bi] is None:
                 continue
+            if self._seg[bi] is not None:
+                # summed, scaled and written back by the request's finish
+                self._seg[bi].wait()
+                self._reqs[bi] = None
+                continue
             mx.wait(self._reqs[bi])
             flat = self._flat[bi]
             if self.average:
@@ -111,6 +151,13 @@ class DistributedData:
             self._reqs[bi] = None
             self._flat[bi] = None
         self._reset_counts()
+
+    def close(self):
+        """Destroy the compressed buckets' requests (none in flight)."""
+        for bi, r in enumerate(self._seg):
+            if r is not None:
+                r.destroy()
+                self._seg[bi] = None
 
 
 def _dt(p):
