@@ -176,6 +176,20 @@ $(ASAN_QSEG): mlsl_amd/csrc/tests/quant_seg_selftest.cpp mlsl_amd/csrc/comm/sche
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -ldl -o $@
 
+# The reduce-scatter prologue over a list of tensors under ASan/UBSan: the host
+# twin over exact-size heap tensors (padding is read through no pointer), and
+# the ring and direct exchanges walked by hand inside plan-sized buffers into an
+# exact-size recv, three starts with the residual carried. Pure host C++.
+ASAN_QRSSEG := $(BUILD)/quant_rs_seg_selftest_asan
+
+asan-quant-rs-seg: $(ASAN_QRSSEG)
+	$(ASAN_QRSSEG)
+
+$(ASAN_QRSSEG): mlsl_amd/csrc/tests/quant_rs_seg_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/comm/quant_plan.cpp mlsl_amd/csrc/core/log.cpp
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $^ -pthread -ldl -o $@
+
 # What a compressed all-gather request refuses at Setup(), through the C++
 # classes and the library as built (no sanitizer; world 1 over TCP).
 QAG_REQUEST := $(BUILD)/quant_ag_request_selftest

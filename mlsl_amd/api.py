@@ -597,6 +597,96 @@ class SegmentedAllReduce:
             self._h = None
 
 
+class SegmentedReduceScatter:
+    """The int8-quantized reduce_scatter (a sum) over a LIST of tensors. With
+    ``total = sum(counts)`` and N ranks in the group, V' is the tensors'
+    concatenation followed by ``N * shard - total`` zeros; it is never built.
+    Bit for bit the request is ``PersistentRequest("reduce_scatter", shard,
+    quantized=True, algo=algo)`` on V': the ``shard`` elements left in
+    ``recv``, the wire, and the error-feedback residual, which is kept across
+    starts, flat in V' order. Only the quantize prologue differs: one pass
+    reads the tensors where they lie and writes all N shards' wires. A shard
+    may begin or end inside a tensor and may be partly or wholly padding;
+    nothing is read for padding.
+
+    counts: elements per tensor, each >= 1; dtype "f32" or "bf16".
+    shard: elements per rank, None (or 0) for ``ceil(total / N)`` (``.shard`` holds
+    the value in use); anything smaller is refused.
+    algo: None takes MLSL_QUANT_RS_ALGO (ring unless set); "ring" or "direct"
+    names it (direct: at most 8 ranks).
+    Refused at creation: any other dtype, an empty list, a zero count,
+    ``shard * N < total``, a compression plugin.
+    ``ShardedOptimizer(grads="in_place")`` reduces its gradients with one such
+    request."""
+
+    def __init__(self, dist, counts, shard=None, dtype="f32", group="global", algo=None):
+        if algo is not None and algo not in QUANT_RS_ALGO:
+            raise ValueError(f"algo={algo!r}: expected None, 'ring' or 'direct'")
+        L = lib()
+        if not hasattr(L, "_rs_segments_declared"):
+            P = ctypes.POINTER
+            L.mlsl_persistent_reduce_scatter_quantized_segments.argtypes = [
+                c_void_p, P(c_size_t), c_size_t, c_size_t, c_int, c_int, c_int, P(c_void_p)]
+            L.mlsl_request_start_segments_recv.argtypes = [c_void_p, P(c_void_p), c_size_t,
+                                                           c_void_p]
+            L.mlsl_request_wait.argtypes = [c_void_p, P(c_void_p)]
+            L.mlsl_request_test.argtypes = [c_void_p, P(c_int)]
+            L.mlsl_request_destroy.argtypes = [c_void_p]
+            for n in ("mlsl_persistent_reduce_scatter_quantized_segments",
+                      "mlsl_request_start_segments_recv", "mlsl_request_wait",
+                      "mlsl_request_test", "mlsl_request_destroy"):
+                getattr(L, n).restype = c_int
+            L._rs_segments_declared = True
+        counts = [int(n) for n in counts]
+        self._h = None
+        self.nseg = len(counts)
+        world = dist.process_count(group)
+        # 0 is the C API's spelling of the default
+        self.shard = int(shard) if shard else (sum(counts) + world - 1) // world
+        h = c_void_p()
+        check(L.mlsl_persistent_reduce_scatter_quantized_segments(
+            dist._h, _sizes(counts), len(counts), self.shard, DTYPE[dtype], GROUP[group],
+            -1 if algo is None else QUANT_RS_ALGO[algo], ctypes.byref(h)))
+        self._h = h
+        self._ptrs = (c_void_p * max(1, len(counts)))()
+
+    def start(self, tensors, recv):
+        """tensors: torch tensors (CPU, or device tensors in device mode),
+        numpy arrays or raw pointers, one per count and in that order; their
+        addresses may change from one start to the next. recv: ``shard``
+        elements of the dtype, overlapping no tensor (not checked)."""
+        n = len(tensors)
+        # another length: the library refuses it, by message
+        arr = self._ptrs if n == self.nseg else (c_void_p * max(1, n))()
+        synced = False
+        for j, t in enumerate(tensors):
+            if hasattr(t, "data_ptr"):
+                # torch: the compute stream is looked up once per start, not
+                # once per tensor (a model has thousands)
+                if not synced and getattr(t, "is_cuda", False):
+                    _sync_compute_stream(t)
+                    synced = True
+                arr[j] = t.data_ptr()
+            else:
+                p = _as_ptr_dtype(t)[0]
+                arr[j] = p.value if p is not None else None   # null: refused below
+        check(lib().mlsl_request_start_segments_recv(self._h, arr, n,
+                                                     _as_ptr_dtype(recv)[0]))
+
+    def wait(self):
+        check(lib().mlsl_request_wait(self._h, None))
+
+    def test(self):
+        done = c_int(0)
+        check(lib().mlsl_request_test(self._h, ctypes.byref(done)))
+        return bool(done.value)
+
+    def destroy(self):
+        if self._h:
+            check(lib().mlsl_request_destroy(self._h))
+            self._h = None
+
+
 class CommBlockInfo:
     def __init__(self, handle):
         self._h = handle

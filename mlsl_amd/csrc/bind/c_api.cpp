@@ -352,6 +352,37 @@ int mlsl_persistent_reduce_scatter_quantized_algo(mlsl_distribution d, size_t re
     C_CATCH
 }
 
+int mlsl_persistent_reduce_scatter_quantized_segments(mlsl_distribution d,
+                                                      const size_t* counts, size_t nseg,
+                                                      size_t shard, mlsl_data_type dt,
+                                                      mlsl_group g, int algo,
+                                                      mlsl_request* out) {
+    C_TRY
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized reduce_scatter over a tensor list supports f32/bf16 only");
+    MLSL_CHECK(nseg > 0 && counts != nullptr,
+               "quantized reduce_scatter over a tensor list needs at least one tensor "
+               "(nseg == 0)");
+    MLSL_CHECK(algo >= -1 && algo <= 1, "unknown quantized reduce_scatter algorithm");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddReduceScatterSegments(std::vector<size_t>(counts, counts + nseg), shard);
+    r->SetCompression(Compression::QUANT_INT8,
+                      Environment::GetEnv().GetQuantizationParams());
+    // -1 names no algorithm: MLSL_QUANT_RS_ALGO decides (ring unless set)
+    r->SetQuantRsAlgo(algo < 0    ? GlobalConfig().quant_rs_algo
+                      : algo == 1 ? QuantRsAlgo::DIRECT
+                                  : QuantRsAlgo::RING);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
+int mlsl_request_start_segments_recv(mlsl_request req, void* const* ptrs, size_t nseg,
+                                     void* recv) {
+    C_TRY static_cast<CommRequest*>(req)->StartSegmentsRecv(ptrs, nseg, recv);
+    C_CATCH
+}
+
 int mlsl_persistent_all_gather(mlsl_distribution d, size_t send_count, mlsl_data_type dt,
                                mlsl_group g, mlsl_request* out) {
     C_TRY CommRequest* r = NewPersistent(d, g, dt);

@@ -250,6 +250,48 @@ int mlsl_hip_dequantize_scatter_tables(const void* wire, void* const* dev_ptrs,
     OPS_CATCH
 }
 
+// quantize-gather of the list padded with zeros to nshards * shard elements,
+// shard by shard: wire j at wire + j * wire_stride, the residual flat.
+int mlsl_hip_quantize_gather_shards(const void* const* ptrs, const size_t* counts, size_t nseg,
+                                    void* err, void* wire, size_t nshards, size_t shard,
+                                    size_t wire_stride, size_t block, int dt, int use_err) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_hip_quantize_gather_shards");
+    size_t total = 0;
+    const std::vector<uint64_t> offs =
+        SegOffsets(counts, nseg, &total, "quantize-gather-shards");
+    DevSegTables tab(offs, ptrs);
+    LaunchQuantizeGatherShards(tab.ptrs, tab.offs, nseg, err, wire, total, nshards, shard,
+                               wire_stride, block, static_cast<DataType>(dt), use_err != 0,
+                               nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_quantize_gather_shards_tables(const void* const* dev_ptrs,
+                                           const uint64_t* dev_offs, size_t nseg, void* err,
+                                           void* wire, size_t total, size_t nshards,
+                                           size_t shard, size_t wire_stride, size_t block,
+                                           int dt, int use_err) {
+    OPS_TRY LaunchQuantizeGatherShards(dev_ptrs, dev_offs, nseg, err, wire, total, nshards,
+                                       shard, wire_stride, block, static_cast<DataType>(dt),
+                                       use_err != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_host_quantize_gather_shards(const void* const* ptrs, const size_t* counts,
+                                     size_t nseg, void* err, void* wire, size_t nshards,
+                                     size_t shard, size_t wire_stride, size_t block, int dt,
+                                     int use_err) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_quantize_gather_shards");
+    size_t total = 0;
+    const std::vector<uint64_t> offs =
+        SegOffsets(counts, nseg, &total, "quantize-gather-shards");
+    HostQuantizeGatherShards(ptrs, offs.data(), nseg, err, wire, total, nshards, shard,
+                             wire_stride, block, static_cast<DataType>(dt), use_err != 0);
+    OPS_CATCH
+}
+
 int mlsl_host_quantize_gather(const void* const* ptrs, const size_t* counts, size_t nseg,
                               void* err, void* wire, size_t block, int dt, int use_err) {
     OPS_TRY CheckQuantBlock(block, "mlsl_host_quantize_gather");

@@ -635,8 +635,10 @@ void IssueSchedule(CommRequest* req, ChunkExec& ce, ncclComm_t comm, hipStream_t
 // run the schedule over the wire; finish into rbuf. `walk` is the only thing
 // the executors differ in: nothing at n=1, the IPC window walker, or the
 // RCCL one.
-// A request over a tensor list (one plan segment, a DEQUANT finish) has no
-// sbuf or rbuf: its prologue and finish go through the tables in `st`.
+// An allreduce over a tensor list (one plan segment, a DEQUANT finish) has no
+// sbuf or rbuf: its prologue and finish go through the tables in `st`. A
+// reduce-scatter over a tensor list has no sbuf: only its prologue does, and
+// the flat reduce-scatter's finish writes rbuf.
 template <class Walk>
 void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec& ce,
                      uint8_t* base, const uint8_t* sbuf, uint8_t* rbuf, hipStream_t s,
@@ -644,6 +646,7 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
     const QuantPlan& p = ce.qplan;
     const DataType dt = req->Dtype();
     const bool seg = req->Segmented();
+    const bool seg_rs = req->SegmentedReduceScatter();
     const size_t nseg = seg ? req->SegPtrs().size() : 0;
     const uint64_t* seg_offs = static_cast<const uint64_t*>(st.seg_dev);
     void** seg_ptrs = seg ? reinterpret_cast<void**>(
@@ -655,9 +658,18 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
         std::memcpy(st.seg_ptrs_pin, req->SegPtrs().data(), nseg * sizeof(void*));
         HIP_CHECKD(hipMemcpyAsync(seg_ptrs, st.seg_ptrs_pin, nseg * sizeof(void*),
                                   hipMemcpyHostToDevice, s));
-        LaunchQuantizeGather(seg_ptrs, seg_offs, nseg, p.residual ? base + p.err_off : nullptr,
-                             base + p.send_seg * p.seg_wire, p.count, p.block, dt, p.residual,
-                             s);
+        if (seg_rs)
+            // all N shards of the padded concatenation in one launch
+            LaunchQuantizeGatherShards(seg_ptrs, seg_offs, nseg,
+                                       p.residual ? base + p.err_off : nullptr,
+                                       base + p.send_seg * p.seg_wire,
+                                       static_cast<size_t>(req->SegOffs().back()), p.nseg,
+                                       p.count, p.seg_wire, p.block, dt, p.residual, s);
+        else
+            LaunchQuantizeGather(seg_ptrs, seg_offs, nseg,
+                                 p.residual ? base + p.err_off : nullptr,
+                                 base + p.send_seg * p.seg_wire, p.count, p.block, dt,
+                                 p.residual, s);
     } else {
         for (size_t j = 0; j < p.nseg; ++j)
             LaunchQuantize(sbuf + j * p.seg_bytes,
@@ -676,7 +688,7 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
             LaunchQuantSumDequant(wires[0], wires[1], rbuf, p.count, p.block, dt, s);
             break;
         case QuantFinish::DEQUANT:
-            if (seg)
+            if (seg && !seg_rs)
                 // round_first: the flat request's bits, then scaled
                 LaunchDequantizeScatter(wires[0], seg_ptrs, seg_offs, nseg, p.count, p.block,
                                         dt, req->PostScale(), /*round_first=*/true, s);
@@ -1039,6 +1051,8 @@ void DeviceCheckSegmentPointers(void* const* ptrs, size_t nseg) {
                        " is not device memory (no staging is built for this request; "
                        "move it to the device)");
 }
+
+bool DeviceIsDevicePointer(const void* p) { return ClassifyPtr(p) == BufClass::DEV; }
 
 double DeviceRequestCommMs(DeviceReqState& st) {
     if (!st.timed || !st.t0_event || st.events.empty()) return -1.0;

@@ -45,6 +45,8 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st);
 // Start of a request over a tensor list: throws, naming the first offender,
 // unless every pointer is device memory (nothing is staged for it).
 void DeviceCheckSegmentPointers(void* const* ptrs, size_t nseg);
+// Whether p is device (or managed) memory, as the check above classifies it.
+bool DeviceIsDevicePointer(const void* p);
 // hipEvent comm time of the last issued request (ms); -1 when not timed
 // (MLSL_STATS off) or not yet complete. Valid after completion.
 double DeviceRequestCommMs(DeviceReqState& st);

@@ -326,6 +326,57 @@ void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, s
     }
 }
 
+void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_offs,
+                              size_t nseg, void* err, void* wire, size_t total,
+                              size_t nshards, size_t shard, size_t wire_stride, size_t block,
+                              DataType dt, bool use_err) {
+    CheckQuantBlock(block, "HostQuantizeGatherShards");
+    CheckSegTables(seg_ptrs, seg_offs, nseg, total, dt, "quantize-gather-shards");
+    MLSL_CHECK(nshards >= 1 && shard >= (total + nshards - 1) / nshards,
+               "quantize-gather-shards: shard * nshards < total (the shards do not hold "
+               "the tensors)");
+    MLSL_CHECK(wire_stride % 4 == 0 &&
+                   wire_stride >= (shard + block - 1) / block * (block + kWireHdr),
+               "quantize-gather-shards: wire_stride is smaller than one shard's wire or "
+               "no multiple of 4");
+    MLSL_CHECK(!use_err || err != nullptr, "quantize-gather-shards: use_err without err");
+    SegCursor cur{seg_offs, nseg};
+    // HostQuantize of every shard of V', reading through the cursor; an element
+    // at or past `total` is 0, and neither a tensor nor the residual is touched
+    // for it
+    for (size_t j = 0; j < nshards; ++j) {
+        const size_t lo = j * shard;
+        uint8_t* w = static_cast<uint8_t*>(wire) + j * wire_stride;
+        if (dt == DataType::F32) {
+            float* e = static_cast<float*>(err);
+            auto in = [&](size_t i) {
+                const size_t k = cur.Seek(i);
+                return static_cast<const float*>(seg_ptrs[cur.s])[k];
+            };
+            QuantizeImpl(
+                [&](size_t i, bool ue) {
+                    i += lo;
+                    return i >= total ? 0.f : ue ? in(i) + e[i] : in(i);
+                },
+                [&](size_t i, float v) { if (i + lo < total) e[i + lo] = v; }, w, shard,
+                block, use_err);
+        } else {
+            uint16_t* e = static_cast<uint16_t*>(err);
+            auto in = [&](size_t i) {
+                const size_t k = cur.Seek(i);
+                return Bf16F(static_cast<const uint16_t*>(seg_ptrs[cur.s])[k]);
+            };
+            QuantizeImpl(
+                [&](size_t i, bool ue) {
+                    i += lo;
+                    return i >= total ? 0.f : ue ? in(i) + Bf16F(e[i]) : in(i);
+                },
+                [&](size_t i, float v) { if (i + lo < total) e[i + lo] = F32B(v); }, w, shard,
+                block, use_err);
+        }
+    }
+}
+
 void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64_t* seg_offs,
                            size_t nseg, size_t count, size_t block, DataType dt,
                            float post_scale, bool round_first) {

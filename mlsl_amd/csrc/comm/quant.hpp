@@ -63,6 +63,19 @@ void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t cou
 void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
                         void* err, void* wire, size_t count, size_t block, DataType dt,
                         bool use_err);
+// Prologue of the quantized reduce-scatter over a list of tensors: V' is V
+// (`total` elements, the tables above) followed by zeros up to nshards * shard
+// elements, and shard j of V' gets HostQuantize's bytes at wire + j *
+// wire_stride and, when use_err, at err + j * shard (the residual is flat in
+// V' order). wire_stride is a multiple of 4 and at least one shard's wire
+// bytes; the bytes between two wires are not written. An element at or past
+// `total` quantizes as 0, is read through no pointer, and its residual is
+// neither read nor written. Bit for bit what LaunchQuantizeGatherShards
+// computes.
+void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_offs,
+                              size_t nseg, void* err, void* wire, size_t total,
+                              size_t nshards, size_t shard, size_t wire_stride, size_t block,
+                              DataType dt, bool use_err);
 // Scatter: every element becomes (q * scale) * post_scale, both products
 // rounded to float and one final rounding for bf16; with post_scale == 1.0f
 // the bits of HostDequantize. Only the tensors are written. Bit for bit what

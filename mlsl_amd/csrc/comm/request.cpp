@@ -78,6 +78,33 @@ void CommRequest::AddAllReduceSegments(const std::vector<size_t>& counts, float 
     post_scale_ = post_scale;
 }
 
+void CommRequest::AddReduceScatterSegments(const std::vector<size_t>& counts, size_t shard) {
+    MLSL_CHECK(!counts.empty(),
+               "quantized reduce_scatter over a tensor list needs at least one tensor "
+               "(nseg == 0)");
+    std::vector<uint64_t> offs(counts.size() + 1, 0);
+    for (size_t j = 0; j < counts.size(); ++j) {
+        MLSL_CHECK(counts[j] > 0, "quantized reduce_scatter over a tensor list: tensor " +
+                                      std::to_string(j) + " has a zero count");
+        offs[j + 1] = offs[j] + counts[j];
+    }
+    const size_t total = static_cast<size_t>(offs.back());
+    const size_t n = static_cast<size_t>(group_->Size());
+    const size_t least = (total + n - 1) / n;
+    if (shard == 0) shard = least;
+    MLSL_CHECK(shard >= least,
+               "quantized reduce_scatter over a tensor list: shard * N < total (shard " +
+                   std::to_string(shard) + " x " + std::to_string(n) + " ranks, " +
+                   std::to_string(total) + " elements; at least " + std::to_string(least) +
+                   ")");
+    MLSL_ADD_OP();
+    spec_.op = CollOp::REDUCE_SCATTER;
+    spec_.count = shard;
+    spec_.rop = ReduceOp::SUM;
+    seg_offs_ = std::move(offs);
+    seg_rs_ = true;
+}
+
 void CommRequest::AddReduce(size_t count, ReduceOp op, int root) {
     MLSL_ADD_OP();
     spec_.op = CollOp::REDUCE;
@@ -488,7 +515,14 @@ void CommRequest::BuildChunks() {
 
 void CommRequest::Setup() {
     MLSL_CHECK(has_op_, "Setup() before describing the op");
-    if (Segmented()) {
+    if (SegmentedReduceScatter()) {
+        // never an exact reduce-scatter of the list behind the caller's back
+        MLSL_CHECK(dtype_ == DataType::F32 || dtype_ == DataType::BF16,
+                   "quantized reduce_scatter over a tensor list supports f32/bf16 only");
+        MLSL_CHECK(comp_ == Compression::QUANT_INT8,
+                   "reduce_scatter over a tensor list exists quantized only "
+                   "(SetCompression(QUANT_INT8))");
+    } else if (Segmented()) {
         // never an exact allreduce of the list behind the caller's back
         MLSL_CHECK(dtype_ == DataType::F32 || dtype_ == DataType::BF16,
                    "quantized all_reduce over a tensor list supports f32/bf16 only");
@@ -497,7 +531,11 @@ void CommRequest::Setup() {
                    "(SetCompression(QUANT_INT8))");
     }
     BuildChunks();
-    // after BuildChunks, whose two-shot refusals come first with their own text
+    // after BuildChunks, whose two-shot and direct refusals come first with
+    // their own text
+    MLSL_CHECK(!SegmentedReduceScatter() || plugin_ == nullptr,
+               "quantized reduce_scatter over a tensor list cannot run with a compression "
+               "plugin (the plugin ABI quantizes one flat buffer); unset lib_path");
     MLSL_CHECK(!Segmented() || plugin_ == nullptr,
                "quantized all_reduce over a tensor list cannot run with a compression "
                "plugin (the plugin ABI quantizes one flat buffer); unset lib_path");
@@ -527,13 +565,51 @@ uint64_t CommRequest::MakeTag(size_t chunk, int phase) const {
 }
 
 void CommRequest::Start(const void* sbuf, void* rbuf) {
+    MLSL_CHECK(!SegmentedReduceScatter(),
+               "this request reduce-scatters a tensor list: start it with "
+               "StartSegmentsRecv (mlsl_request_start_segments_recv)");
     MLSL_CHECK(!Segmented(),
                "this request runs over a tensor list: start it with StartSegments "
                "(mlsl_request_start_segments)");
     StartCommon(sbuf, rbuf);
 }
 
+void CommRequest::StartSegmentsRecv(void* const* ptrs, size_t nseg, void* recv) {
+    MLSL_CHECK(SegmentedReduceScatter(),
+               "StartSegmentsRecv on a request that was not described as a "
+               "reduce_scatter over a tensor list");
+    MLSL_CHECK(setup_done_, "Start() before Setup()");
+    ReqState st = state_.load(std::memory_order_acquire);
+    MLSL_CHECK(st == ReqState::IDLE || st == ReqState::DONE,
+               "Start() while request in flight");
+    const size_t want = seg_offs_.size() - 1;
+    MLSL_CHECK(nseg == want, "reduce_scatter start with " + std::to_string(nseg) +
+                                 " tensors on a request created over " +
+                                 std::to_string(want) + " (nseg differs from creation)");
+    MLSL_CHECK(ptrs != nullptr, "reduce_scatter start over a tensor list: null pointer list");
+    for (size_t j = 0; j < nseg; ++j)
+        MLSL_CHECK(ptrs[j] != nullptr, "reduce_scatter start over a tensor list: tensor " +
+                                           std::to_string(j) + " is null");
+    MLSL_CHECK(recv != nullptr, "reduce_scatter start over a tensor list: recv is null");
+    // refused before anything of the last start is overwritten
+    if (Context::Get().DeviceMode()) {
+        for (size_t j = 0; j < nseg; ++j)
+            MLSL_CHECK(DeviceIsDevicePointer(ptrs[j]),
+                       "reduce_scatter start over a tensor list: tensor " + std::to_string(j) +
+                           " is not device memory (no staging is built for this request; "
+                           "move it to the device)");
+        MLSL_CHECK(DeviceIsDevicePointer(recv),
+                   "reduce_scatter start over a tensor list: recv is not device memory (no "
+                   "staging is built for this request; move it to the device)");
+    }
+    seg_ptrs_.assign(ptrs, ptrs + nseg);
+    StartCommon(nullptr, recv);
+}
+
 void CommRequest::StartSegments(void* const* ptrs, size_t nseg) {
+    MLSL_CHECK(!SegmentedReduceScatter(),
+               "this request reduce-scatters a tensor list and needs a recv buffer: start "
+               "it with StartSegmentsRecv (mlsl_request_start_segments_recv)");
     MLSL_CHECK(Segmented(), "StartSegments on a request that was not described over a "
                             "tensor list");
     MLSL_CHECK(setup_done_, "Start() before Setup()");
@@ -686,9 +762,16 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
         };
         if (compressed && !ce.prologue_done) {
             // quantize user send (+ residual, where the plan has one) into
-            // the wire; over a tensor list (one plan segment) straight from the
-            // tensors
-            if (Segmented())
+            // the wire; over a tensor list straight from the tensors: an
+            // allreduce's one plan segment, or all N shards of a reduce-scatter's
+            // padded concatenation in one pass
+            if (SegmentedReduceScatter())
+                HostQuantizeGatherShards(seg_ptrs_.data(), seg_offs_.data(), seg_ptrs_.size(),
+                                         qp.residual ? wire + qp.err_off : nullptr,
+                                         wire + qp.send_seg * qp.seg_wire,
+                                         static_cast<size_t>(seg_offs_.back()), qp.nseg,
+                                         qp.count, qp.seg_wire, qp.block, dtype_, qp.residual);
+            else if (Segmented())
                 HostQuantizeGather(seg_ptrs_.data(), seg_offs_.data(), seg_ptrs_.size(),
                                    qp.residual ? wire + qp.err_off : nullptr,
                                    wire + qp.send_seg * qp.seg_wire, qp.count, qp.block,
@@ -814,7 +897,9 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                                                     qp.block, dtype_);
                                 break;
                             case QuantFinish::DEQUANT:
-                                if (Segmented())
+                                // (a reduce-scatter over a list on a group of
+                                // one finishes into recv like a flat one)
+                                if (Segmented() && !SegmentedReduceScatter())
                                     HostDequantizeScatter(wires[0], seg_ptrs_.data(),
                                                           seg_offs_.data(), seg_ptrs_.size(),
                                                           qp.count, qp.block, dtype_,

@@ -102,6 +102,17 @@ class CommRequest {
     // the finish multiplies by post_scale. Needs SetCompression(QUANT_INT8)
     // on f32/bf16 without a plugin, or Setup() fails; runs with StartSegments.
     void AddAllReduceSegments(const std::vector<size_t>& counts, float post_scale);
+    // The quantized reduce-scatter (SUM) over a list of tensors of counts[j] >=
+    // 1 elements: bit for bit AddReduceScatter(shard) + SetCompression on V',
+    // the tensors' concatenation followed by zeros up to N * shard elements,
+    // which is never built (values, wire and the flat residual of N * shard
+    // elements). shard == 0 takes ceil(total / N); a smaller shard than that is
+    // refused. Only the quantize prologue differs
+    // (quant.hpp, HostQuantizeGatherShards): a shard may begin or end inside a
+    // tensor or be padding only, and padding is read through no pointer. Needs
+    // SetCompression(QUANT_INT8) on f32/bf16 without a plugin, or Setup()
+    // fails; runs with StartSegmentsRecv.
+    void AddReduceScatterSegments(const std::vector<size_t>& counts, size_t shard);
     void AddReduce(size_t count, ReduceOp op, int root);
     void AddReduceScatter(size_t recv_count, ReduceOp op);
     void AddAllGather(size_t send_count);
@@ -153,6 +164,10 @@ class CommRequest {
     // this start (they may differ from the last one's). In device mode every
     // one must be device memory: nothing is staged for such a request.
     void StartSegments(void* const* ptrs, size_t nseg);
+    // Start of an AddReduceScatterSegments request: this start's nseg tensor
+    // pointers and recv, `shard` elements that must not overlap any tensor (not
+    // detected). In device mode the tensors and recv must be device memory.
+    void StartSegmentsRecv(void* const* ptrs, size_t nseg, void* recv);
     void* Wait();                         // returns result pointer
     bool Test();                          // true when complete
     size_t GetTmpBytes() const { return total_tmp_bytes_; }
@@ -189,9 +204,11 @@ class CommRequest {
         dev_sbuf_ = s;
         dev_rbuf_ = r;
     }
-    // AddAllReduceSegments requests: nseg + 1 prefix offsets in elements
-    // (fixed at description), this start's nseg pointers, the finish's factor.
+    // Requests over a tensor list, of two kinds (AddAllReduceSegments,
+    // AddReduceScatterSegments): nseg + 1 prefix offsets in elements (fixed at
+    // description), this start's nseg pointers, the allreduce finish's factor.
     bool Segmented() const { return !seg_offs_.empty(); }
+    bool SegmentedReduceScatter() const { return Segmented() && seg_rs_; }
     const std::vector<uint64_t>& SegOffs() const { return seg_offs_; }
     const std::vector<void*>& SegPtrs() const { return seg_ptrs_; }
     float PostScale() const { return post_scale_; }
@@ -216,7 +233,8 @@ class CommRequest {
     bool qag_accumulate_ = false;
     QuantArAlgo qar_algo_ = QuantArAlgo::RING;   // meaningful once qar_named_
     bool qar_named_ = false;   // false: MLSL_QUANT_AR_ALGO decides at Setup()
-    std::vector<uint64_t> seg_offs_;   // empty unless AddAllReduceSegments
+    std::vector<uint64_t> seg_offs_;   // empty unless Add*Segments
+    bool seg_rs_ = false;              // AddReduceScatterSegments
     std::vector<void*> seg_ptrs_;      // per StartSegments
     float post_scale_ = 1.0f;
 

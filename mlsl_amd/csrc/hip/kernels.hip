@@ -1606,15 +1606,109 @@ __device__ __forceinline__ void ForEachSegElem(const SegTable& t, P ptrs,
     }
 }
 
+// One wire block of a list: the n >= 1 elements that start at V[base], `cur`
+// at the tensor of V[base], the block's residual at eb (null without USE_ERR).
+// Writes the header, the payload (zero from n up to block_elems) and the
+// residual of the n elements. QuantizeKernel's arithmetic per element, on one
+// of three paths, chosen per block: 256 elements inside one tensor with the
+// tensor address and eb both 16-byte aligned stay in registers, four
+// consecutive elements per lane read once; a block inside one tensor at an
+// aligned address takes the 4-wide loop; any other walks the table.
+template <typename T, bool USE_ERR, typename P>
+__device__ __forceinline__ void QuantizeSegBlock(const SegTable& tab, P ptrs,
+                                                 const SegCursor<const T>& cur, size_t base,
+                                                 size_t n, size_t block_elems, T* eb,
+                                                 uint8_t* wblock, int lane) {
+    using V4 = std::conditional_t<sizeof(T) == 4, float4_ev, ushort4_t>;
+    int8_t* payload = reinterpret_cast<int8_t*>(wblock + kWireHdr);
+    const T* in = cur.ptr + (base - cur.lo);   // V[base], if the block is whole
+    const bool whole = base + n <= cur.hi;
+    const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+    const bool regs = block_elems == kFastBlock && n == kFastBlock &&
+                      (reinterpret_cast<uintptr_t>(eb) & 15) == 0;
+
+    if (whole && aligned && regs) {
+        const V4 a = *reinterpret_cast<const V4*>(in + lane * 4);
+        V4 e{};
+        if (USE_ERR) e = *reinterpret_cast<const V4*>(eb + lane * 4);
+        float v[4];
+        float m = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = Decode<T>(a[k]);
+            if (USE_ERR) v[k] += Decode<T>(e[k]);
+            m = fmaxf(m, fabsf(v[k]));
+        }
+        const float scale = QScale(WaveMax(m));
+        if (lane == 0) WriteWireHeader(wblock, scale);
+        const float inv = 1.f / scale;
+        uint32_t packed = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float q = QRound(v[k], inv);
+            packed |= QPack(q, k);
+            if (USE_ERR) e[k] = Encode<T>(v[k] - q * scale);
+        }
+        QStore<4>(payload, lane * 4, packed);
+        if (USE_ERR) StoreVec<false>(e, eb + lane * 4);
+    } else if (whole && aligned) {
+        auto value = [&](size_t i) {
+            float v = Decode(in[i]);
+            if (USE_ERR) v += Decode(eb[i]);
+            return v;
+        };
+        float m = 0.f;
+        ForEachBlockElem(n, true, lane, [&](size_t i, auto w) {
+#pragma unroll
+            for (int k = 0; k < decltype(w)::value; ++k)
+                m = fmaxf(m, fabsf(value(i + k)));
+        });
+        const float scale = QScale(WaveMax(m));
+        if (lane == 0) WriteWireHeader(wblock, scale);
+        const float inv = 1.f / scale;
+        ForEachBlockElem(n, true, lane, [&](size_t i, auto w) {
+            constexpr int W = decltype(w)::value;
+            uint32_t packed = 0;
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+                const float v = value(i + k);
+                const float q = QRound(v, inv);
+                packed |= QPack(q, k);
+                if (USE_ERR) eb[i + k] = Encode<T>(v - q * scale);
+            }
+            QStore<W>(payload, i, packed);
+        });
+    } else {
+        auto value = [&](size_t i, const T* p) {
+            float v = Decode(*p);
+            if (USE_ERR) v += Decode(eb[i]);
+            return v;
+        };
+        float m = 0.f;
+        ForEachSegElem<const T>(tab, ptrs, cur, base, n, lane,
+                                [&](size_t i, const T* p) {
+                                    m = fmaxf(m, fabsf(value(i, p)));
+                                });
+        const float scale = QScale(WaveMax(m));
+        if (lane == 0) WriteWireHeader(wblock, scale);
+        const float inv = 1.f / scale;
+        ForEachSegElem<const T>(tab, ptrs, cur, base, n, lane,
+                                [&](size_t i, const T* p) {
+                                    const float v = value(i, p);
+                                    const float q = QRound(v, inv);
+                                    payload[i] = static_cast<int8_t>(q);
+                                    if (USE_ERR) eb[i] = Encode<T>(v - q * scale);
+                                });
+    }
+    // whatever the block holds past its n elements
+    for (size_t i = n + lane; i < block_elems; i += 64) payload[i] = 0;
+}
+
 template <typename T, bool USE_ERR>
 __global__ void QuantizeGatherKernel(const T* const* __restrict__ ptrs, SegTable tab,
                                      T* __restrict__ err, uint8_t* __restrict__ wire,
                                      size_t count, size_t block_elems) {
-    using V4 = std::conditional_t<sizeof(T) == 4, float4_ev, ushort4_t>;
     SegCursor<const T> cur;
-    // whole 256-blocks may stay in registers when err takes vector accesses
-    const bool regs = block_elems == kFastBlock &&
-                      (!USE_ERR || (reinterpret_cast<uintptr_t>(err) & 15) == 0);
     ForEachWaveBlock((count + block_elems - 1) / block_elems, [&](size_t vblk, int lane) {
         // uniform across the wave: the bisection and the table reads stay in
         // scalar registers
@@ -1622,89 +1716,55 @@ __global__ void QuantizeGatherKernel(const T* const* __restrict__ ptrs, SegTable
                                 static_cast<uint32_t>(vblk >> 32))) << 32) |
                            __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vblk));
         const size_t base = blk * block_elems;
-        const size_t n = min(block_elems, count - base);
-        uint8_t* wblock = wire + blk * (block_elems + kWireHdr);
-        int8_t* payload = reinterpret_cast<int8_t*>(wblock + kWireHdr);
         cur.Seek(tab, ptrs, base);
-        const T* in = cur.ptr + (base - cur.lo);   // V[base], if the block is whole
-        const bool whole = base + n <= cur.hi;
-        const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0;
+        QuantizeSegBlock<T, USE_ERR>(tab, ptrs, cur, base, min(block_elems, count - base),
+                                     block_elems, USE_ERR ? err + base : nullptr,
+                                     wire + blk * (block_elems + kWireHdr), lane);
+    });
+}
 
-        if (whole && aligned && regs && n == kFastBlock) {
-            // four consecutive elements per lane, read once and kept in
-            // registers: QuantizeKernel's arithmetic per element
-            const V4 a = *reinterpret_cast<const V4*>(in + lane * 4);
-            V4 e{};
-            if (USE_ERR) e = *reinterpret_cast<const V4*>(err + base + lane * 4);
-            float v[4];
-            float m = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[j] = Decode<T>(a[j]);
-                if (USE_ERR) v[j] += Decode<T>(e[j]);
-                m = fmaxf(m, fabsf(v[j]));
-            }
-            const float scale = QScale(WaveMax(m));
-            if (lane == 0) WriteWireHeader(wblock, scale);
-            const float inv = 1.f / scale;
-            uint32_t packed = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float q = QRound(v[j], inv);
-                packed |= QPack(q, j);
-                if (USE_ERR) e[j] = Encode<T>(v[j] - q * scale);
-            }
-            QStore<4>(payload, lane * 4, packed);
-            if (USE_ERR) StoreVec<false>(e, err + base + lane * 4);
-        } else if (whole && aligned) {
-            // QuantizeKernel's block body on this tensor
-            auto value = [&](size_t i) {
-                float v = Decode(in[i]);
-                if (USE_ERR) v += Decode(err[base + i]);
-                return v;
-            };
-            float m = 0.f;
-            ForEachBlockElem(n, true, lane, [&](size_t i, auto w) {
-#pragma unroll
-                for (int j = 0; j < decltype(w)::value; ++j)
-                    m = fmaxf(m, fabsf(value(i + j)));
-            });
-            const float scale = QScale(WaveMax(m));
-            if (lane == 0) WriteWireHeader(wblock, scale);
-            const float inv = 1.f / scale;
-            ForEachBlockElem(n, true, lane, [&](size_t i, auto w) {
-                constexpr int W = decltype(w)::value;
-                uint32_t packed = 0;
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    const float v = value(i + j);
-                    const float q = QRound(v, inv);
-                    packed |= QPack(q, j);
-                    if (USE_ERR) err[base + i + j] = Encode<T>(v - q * scale);
-                }
-                QStore<W>(payload, i, packed);
-            });
-        } else {
-            auto value = [&](size_t i, const T* p) {
-                float v = Decode(*p);
-                if (USE_ERR) v += Decode(err[base + i]);
-                return v;
-            };
-            float m = 0.f;
-            ForEachSegElem<const T>(tab, ptrs, cur, base, n, lane, [&](size_t i, const T* p) {
-                m = fmaxf(m, fabsf(value(i, p)));
-            });
-            const float scale = QScale(WaveMax(m));
-            if (lane == 0) WriteWireHeader(wblock, scale);
-            const float inv = 1.f / scale;
-            ForEachSegElem<const T>(tab, ptrs, cur, base, n, lane, [&](size_t i, const T* p) {
-                const float v = value(i, p);
-                const float q = QRound(v, inv);
-                payload[i] = static_cast<int8_t>(q);
-                if (USE_ERR) err[base + i] = Encode<T>(v - q * scale);
-            });
+// The prologue of the reduce-scatter over a list: V' is the concatenation V
+// (total elements) followed by zeros up to nshards * shard, and shard j, V'[j *
+// shard, (j + 1) * shard), is quantized on a block grid of its own into wire +
+// j * wire_stride, with the residual flat in V' order. One launch covers all
+// shards: wire block `blk` of the launch is block blk % bps of shard blk / bps,
+// so block bases still ascend with blk and the cursor only moves forward.
+// What differs from QuantizeGatherKernel: a block's base in V' is j * shard +
+// b * block_elems, no multiple of anything, so the alignment of the tensor
+// address AND of err + base is looked at per block; and an element at or past
+// `total` is the value 0 and is never looked up: only the block's `real`
+// elements go through the table or touch the residual (a padding element's
+// residual is +0 and stays so), and a block at or past `total` is all zero.
+template <typename T, bool USE_ERR>
+__global__ void QuantizeGatherShardsKernel(const T* const* __restrict__ ptrs, SegTable tab,
+                                           T* __restrict__ err, uint8_t* __restrict__ wire,
+                                           size_t total, uint32_t nshards, size_t shard,
+                                           size_t wire_stride, size_t block_elems) {
+    SegCursor<const T> cur;
+    const uint32_t bps = static_cast<uint32_t>((shard + block_elems - 1) / block_elems);
+    ForEachWaveBlock(static_cast<size_t>(nshards) * bps, [&](size_t vblk, int lane) {
+        // uniform across the wave (the launcher keeps the block count in 32 bits)
+        const uint32_t blk = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vblk));
+        const uint32_t j = blk / bps, b = blk - j * bps;
+        const size_t in_shard = static_cast<size_t>(b) * block_elems;
+        const size_t base = static_cast<size_t>(j) * shard + in_shard;
+        const size_t n = min(block_elems, shard - in_shard);
+        uint8_t* wblock = wire + j * wire_stride + static_cast<size_t>(b) * (block_elems + kWireHdr);
+        int8_t* payload = reinterpret_cast<int8_t*>(wblock + kWireHdr);
+        if (base >= total) {
+            // padding only: nothing is read. An early return on purpose: with
+            // the count of real elements written as one expression, base <
+            // total ? min(n, total - base) : 0, blocks past `total` were seen
+            // to go through the table on the device.
+            if (lane == 0) WriteWireHeader(wblock, QScale(0.f));
+            for (size_t i = lane * 4; i < block_elems; i += 256) QStore<4>(payload, i, 0);
+            return;
         }
-        for (size_t i = n + lane; i < block_elems; i += 64) payload[i] = 0;
+        // the block's elements that exist: at least one from here on
+        const size_t real = min(n, total - base);
+        cur.Seek(tab, ptrs, base);
+        QuantizeSegBlock<T, USE_ERR>(tab, ptrs, cur, base, real, block_elems,
+                                     USE_ERR ? err + base : nullptr, wblock, lane);
     });
 }
 
@@ -1786,6 +1846,43 @@ void LaunchQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs,
             QuantizeGatherKernel<unsigned short, UE><<<grid, dim3(kBlock), 0, stream>>>(
                 reinterpret_cast<const unsigned short* const*>(seg_ptrs), tab,
                 static_cast<unsigned short*>(err), w, count, block_elems);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+void LaunchQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_offs,
+                                size_t nseg, void* err, void* wire, size_t total,
+                                size_t nshards, size_t shard, size_t wire_stride,
+                                size_t block_elems, DataType dt, bool use_err,
+                                hipStream_t stream) {
+    CheckQuantBlock(block_elems, "LaunchQuantizeGatherShards");
+    CheckSegArgs(seg_ptrs, seg_offs, nseg, total, dt, "quantize-gather-shards");
+    MLSL_CHECK(nshards >= 1 && shard >= (total + nshards - 1) / nshards,
+               "quantize-gather-shards: shard * nshards < total (the shards do not hold "
+               "the tensors)");
+    const size_t bps = NumBlocks(shard, block_elems);
+    MLSL_CHECK(bps * nshards <= 0xffffffffull,
+               "quantize-gather-shards: more than 2^32 wire blocks");
+    // a wire block needs its header's and its payload words' alignment only
+    MLSL_CHECK(wire_stride % 4 == 0 && wire_stride >= bps * (block_elems + kWireHdr),
+               "quantize-gather-shards: wire_stride is smaller than one shard's wire or "
+               "no multiple of 4");
+    MLSL_CHECK(!use_err || err != nullptr, "quantize-gather-shards: use_err without err");
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const dim3 grid = WaveGrid(bps * nshards);
+    uint8_t* w = static_cast<uint8_t*>(wire);
+    DispatchBool(use_err, [&](auto ue) {
+        constexpr bool UE = decltype(ue)::value;
+        if (dt == DataType::F32)
+            QuantizeGatherShardsKernel<float, UE><<<grid, dim3(kBlock), 0, stream>>>(
+                reinterpret_cast<const float* const*>(seg_ptrs), tab,
+                static_cast<float*>(err), w, total, static_cast<uint32_t>(nshards), shard,
+                wire_stride, block_elems);
+        else
+            QuantizeGatherShardsKernel<unsigned short, UE><<<grid, dim3(kBlock), 0, stream>>>(
+                reinterpret_cast<const unsigned short* const*>(seg_ptrs), tab,
+                static_cast<unsigned short*>(err), w, total, static_cast<uint32_t>(nshards),
+                shard, wire_stride, block_elems);
     });
     HIP_CHECK(hipGetLastError());
 }

@@ -114,6 +114,21 @@ void LaunchDequantizeSegments(const void* wire, size_t nseg, void* out, size_t c
 void LaunchQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
                           void* err, void* wire, size_t count, size_t block_elems,
                           DataType dt, bool use_err, hipStream_t stream);
+// Prologue of the quantized reduce-scatter over a list of tensors. V' is V (the
+// tables above, `total` elements) followed by zeros up to nshards * shard
+// elements (shard * nshards >= total). One launch writes, for every shard j,
+// the bytes LaunchQuantize writes for V'[j * shard, (j + 1) * shard) to wire +
+// j * wire_stride (wire_stride: a multiple of 4, at least one shard's wire
+// bytes; the bytes between two shards' wires are not written) and, when
+// use_err, to err + j * shard: the residual is flat in V' order, nshards * shard
+// elements. A shard may begin or end inside a tensor. An element at or past
+// `total` quantizes as 0, is read through no pointer, and its residual, +0
+// from the start, is neither read nor written.
+void LaunchQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_offs,
+                                size_t nseg, void* err, void* wire, size_t total,
+                                size_t nshards, size_t shard, size_t wire_stride,
+                                size_t block_elems, DataType dt, bool use_err,
+                                hipStream_t stream);
 // Scatter: every element becomes Encode((q * scale) * post_scale), both
 // products rounded to float and one final rounding for bf16: with post_scale
 // == 1.0f the bits of LaunchDequantize. The wire is only read and no byte

@@ -169,6 +169,35 @@ int mlsl_persistent_reduce_scatter_quantized_algo(mlsl_distribution d, size_t re
                                                   mlsl_data_type dt, mlsl_reduction op,
                                                   mlsl_group g, mlsl_quant_rs_algo algo,
                                                   mlsl_request* out);
+/* The int8-quantized reduce-scatter (a sum) over a LIST of nseg tensors of
+ * counts[j] >= 1 elements each. With total = sum(counts) and N ranks in the
+ * group, V' is the tensors' concatenation followed by N * shard - total zeros;
+ * it is never built. Bit for bit this is mlsl_persistent_reduce_scatter_quantized_algo
+ * with recv_count = shard on V': the shard elements left in recv, the wire, and
+ * the residual (flat in V' order, N * shard elements, kept across starts).
+ * shard == 0 takes ceil(total / N); shard * N < total fails. A shard may begin
+ * or end inside a tensor, and may be partly or wholly padding; nothing is read
+ * through any pointer for padding. algo: -1 takes MLSL_QUANT_RS_ALGO, 0 the
+ * ring, 1 direct (limits as above). Only the quantize prologue differs from
+ * the flat request: it reads the tensors where they lie, all N shards in one
+ * pass.
+ * mlsl_request_start_segments_recv gives the pointers, which may change between
+ * starts and need the element's alignment only, and recv (shard elements of
+ * dt), which must not overlap any tensor; that is not checked. In device mode
+ * the tensors and recv must be device memory: nothing is staged.
+ * wait/test/destroy as for any request; mlsl_request_start and
+ * mlsl_request_start_segments on such a request fail, as does this start on
+ * any other request.
+ * Fails at creation unless dt is f32 or bf16, for nseg == 0 or a zero count,
+ * and with a compression plugin (lib_path), whose ABI quantizes one flat
+ * buffer. */
+int mlsl_persistent_reduce_scatter_quantized_segments(mlsl_distribution d,
+                                                      const size_t* counts, size_t nseg,
+                                                      size_t shard, mlsl_data_type dt,
+                                                      mlsl_group g, int algo,
+                                                      mlsl_request* out);
+int mlsl_request_start_segments_recv(mlsl_request req, void* const* ptrs, size_t nseg,
+                                     void* recv);
 int mlsl_persistent_all_gather(mlsl_distribution d, size_t send_count, mlsl_data_type dt,
                                mlsl_group g, mlsl_request* out);
 /* int8-quantized all-gather (block size from mlsl_set_quant_params). Every

@@ -92,6 +92,7 @@ void LaunchQuantSumRequantN(const void* const* w, int nw, void* dst, size_t unit
 }
 void LaunchDequantizeSegments(const void* w, size_t nseg, void* out, size_t n, size_t blk, DataType dt, bool acc, hipStream_t st) STUB(LaunchDequantizeSegments, w, nseg, out, n, blk, dt, acc, st)
 void LaunchQuantizeGather(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGather, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st)
+void LaunchQuantizeGatherShards(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t total, size_t nshards, size_t shard, size_t stride, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGatherShards, ptrs, offs, nseg, err, w, total, nshards, shard, stride, blk, dt, use_err, st)
 void LaunchDequantizeScatter(const void* w, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, size_t blk, DataType dt, float post, bool round_first, hipStream_t st) STUB(LaunchDequantizeScatter, w, ptrs, offs, nseg, n, blk, dt, post, round_first, st)
 void LaunchPack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchPack, s, d, pd, dt, st)
 void LaunchUnpack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchUnpack, s, d, pd, dt, st)

@@ -71,6 +71,19 @@ def _lib():
                                                          c.c_int, c.c_float, c.c_int]
         L.mlsl_hip_quantize_gather_tables.restype = c.c_int
         L.mlsl_hip_dequantize_scatter_tables.restype = c.c_int
+        L.mlsl_hip_quantize_gather_shards.argtypes = [c.POINTER(c.c_void_p),
+                                                      c.POINTER(c.c_size_t), c.c_size_t,
+                                                      c.c_void_p, c.c_void_p, c.c_size_t,
+                                                      c.c_size_t, c.c_size_t, c.c_size_t,
+                                                      c.c_int, c.c_int]
+        L.mlsl_host_quantize_gather_shards.argtypes = \
+            L.mlsl_hip_quantize_gather_shards.argtypes
+        L.mlsl_hip_quantize_gather_shards_tables.argtypes = [
+            c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_size_t,
+            c.c_size_t, c.c_size_t, c.c_size_t, c.c_size_t, c.c_int, c.c_int]
+        for n in ("mlsl_hip_quantize_gather_shards", "mlsl_host_quantize_gather_shards",
+                  "mlsl_hip_quantize_gather_shards_tables"):
+            getattr(L, n).restype = c.c_int
         for n in ("mlsl_hip_quantize_gather", "mlsl_host_quantize_gather",
                   "mlsl_hip_dequantize_scatter", "mlsl_host_dequantize_scatter"):
             getattr(L, n).restype = c.c_int
@@ -288,6 +301,60 @@ def dequantize_scatter(wire, tensors, counts, block=256, dtype=None, post_scale=
                                              post_scale, 1 if round_first else 0))
 
 
+def _shard_args(total, nshards, shard, wire_stride, block):
+    """(nshards, shard, wire_stride) checked; wire_stride=None is one shard's
+    wire bytes rounded up to 16."""
+    nshards, shard = int(nshards), int(shard)
+    if nshards < 1 or shard * nshards < total:
+        raise ValueError(f"shard * nshards < total: {nshards} shards of {shard} elements "
+                         f"do not hold {total}")
+    need = wire_bytes(shard, block)
+    if wire_stride is None:
+        wire_stride = (need + 15) // 16 * 16
+    wire_stride = int(wire_stride)
+    if wire_stride < need or wire_stride % 4:
+        raise ValueError(f"wire_stride={wire_stride}: a multiple of 4 of at least {need} "
+                         "bytes (one shard's wire) is needed")
+    return nshards, shard, wire_stride
+
+
+def quantize_gather_shards(tensors, counts, wire, nshards, shard, err=None, block=256,
+                           dtype=None, wire_stride=None):
+    """`quantize_gather` shard by shard, in one launch: with V' the
+    concatenation of `tensors` followed by zeros up to nshards * shard
+    elements (never built), shard j = V'[j*shard:(j+1)*shard] gets exactly the
+    bytes `quantize` writes for it, at wire + j * wire_stride, and the residual
+    `err` (if given: nshards * shard elements, flat in V' order) at err + j *
+    shard. wire_stride=None is wire_bytes(shard, block) rounded up to 16; the
+    bytes between two shards' wires are left alone. A shard may begin or end
+    inside a tensor or be padding only. A padding element quantizes as 0, is
+    read through no pointer, and its residual (+0 from the start) is neither
+    read nor written. This is the prologue of `SegmentedReduceScatter`."""
+    _check_block(block)
+    ptrs, cnts, nseg, total, dt = _seg_tables(tensors, counts, dtype)
+    nshards, shard, wire_stride = _shard_args(total, nshards, shard, wire_stride, block)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather_shards(ptrs, cnts, nseg, ep, wp, nshards, shard,
+                                                 wire_stride, block, DTYPE[dt],
+                                                 1 if err is not None else 0))
+
+
+def quantize_gather_shards_tables(dev_ptrs, dev_offs, nseg, total, wire, nshards, shard,
+                                  err=None, block=256, dtype="f32", wire_stride=None):
+    """`quantize_gather_shards` over tables in DEVICE memory; see
+    `quantize_gather_tables` (dev_offs runs from 0 to total)."""
+    _check_block(block)
+    nshards, shard, wire_stride = _shard_args(total, nshards, shard, wire_stride, block)
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    fp, _ = _as_ptr_dtype(dev_offs)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather_shards_tables(
+        pp, fp, nseg, ep, wp, total, nshards, shard, wire_stride, block, DTYPE[dtype],
+        1 if err is not None else 0))
+
+
 def quantize_gather_tables(dev_ptrs, dev_offs, nseg, count, wire, err=None, block=256,
                            dtype="f32"):
     """`quantize_gather` over tables the caller keeps in DEVICE memory, as a
@@ -345,6 +412,19 @@ def host_quantize_gather(arrays, counts, wire, err=None, block=256, dtype="f32")
     ep = None if err is None else _host_buf(err, total * _ELEM_BYTES[dtype], "err")
     check(_lib().mlsl_host_quantize_gather(ptrs, cnts, nseg, ep, wp, block, DTYPE[dtype],
                                            1 if err is not None else 0))
+
+
+def host_quantize_gather_shards(arrays, counts, wire, nshards, shard, err=None, block=256,
+                                dtype="f32", wire_stride=None):
+    """Host twin of `quantize_gather_shards` on numpy arrays: the same bits."""
+    _check_block(block)
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays")
+    nshards, shard, wire_stride = _shard_args(total, nshards, shard, wire_stride, block)
+    wp = _host_buf(wire, (nshards - 1) * wire_stride + wire_bytes(shard, block), "wire")
+    ep = None if err is None else _host_buf(err, nshards * shard * _ELEM_BYTES[dtype], "err")
+    check(_lib().mlsl_host_quantize_gather_shards(ptrs, cnts, nseg, ep, wp, nshards, shard,
+                                                  wire_stride, block, DTYPE[dtype],
+                                                  1 if err is not None else 0))
 
 
 def host_dequantize_scatter(wire, arrays, counts, block=256, dtype="f32", post_scale=1.0,

@@ -30,6 +30,10 @@ With ``compression="int8"`` that reduce_scatter travels as int8 wire blocks
 with error feedback (one persistent request, so the residual carries over
 from step to step). The parameter all_gather is exact unless
 ``ag_compression="int8"`` is given: see the class.
+With ``grads="in_place"`` on top of that the int8 wire is built straight from
+the gradients where they lie (one ``mx.SegmentedReduceScatter`` over
+``[p.grad ...]``): the flat gradient buffer, as large as the model, and the
+copy of every gradient into it are gone.
 """
 import torch
 
@@ -70,7 +74,7 @@ class ShardedOptimizer:
 
     def __init__(self, params, opt_cls, dist=None, group="data",
                  reduce="none", average=True, compression="none", rs_algo=None,
-                 ag_compression="none", **opt_kwargs):
+                 ag_compression="none", grads="copy", **opt_kwargs):
         """reduce: "none" (grads already reduced, e.g. by DistributedData)
         or "rs" (this wrapper reduce-scatters raw local grads itself).
         compression: "none", or "int8" for the quantized reduce_scatter
@@ -82,7 +86,16 @@ class ShardedOptimizer:
         at most 8 ranks, N-1 shard-wires of scratch instead of 2).
         ag_compression: "none" (exact parameter all_gather), or "int8": the
         quantized, accumulating all_gather of master - replica described in
-        the class docstring (f32 or bf16 parameters)."""
+        the class docstring (f32 or bf16 parameters).
+        grads: "copy" gathers every gradient into one flat buffer as large as
+        the parameters (``flat_grad``) before it is reduced. "in_place" (needs
+        reduce="rs" and compression="int8"; any rs_algo and ag_compression)
+        keeps no such buffer at world > 1: the quantized reduce_scatter reads
+        the gradients where they lie and leaves the owned shard in
+        ``own_grad``, a tensor of its own. The parameters' bits are those of
+        "copy". A parameter without a gradient counts as zeros (one cached
+        zeros_like per such parameter) and a non-contiguous gradient goes
+        through .contiguous(). On a group of one nothing changes."""
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
@@ -107,6 +120,15 @@ class ShardedOptimizer:
         if ag_compression not in ("none", "int8"):
             raise ValueError(f"ag_compression={ag_compression!r}: expected 'none' or 'int8'")
         self.ag_compression = ag_compression
+        if grads not in ("copy", "in_place"):
+            raise ValueError(f"grads={grads!r}: expected 'copy' or 'in_place'")
+        if grads == "in_place" and reduce != "rs":
+            raise ValueError('grads="in_place" reads the gradients in the reduce_scatter: '
+                             'it needs reduce="rs"')
+        if grads == "in_place" and compression != "int8":
+            raise ValueError('grads="in_place" builds the int8 wire from the gradients: '
+                             'it needs compression="int8"')
+        self.grads = grads
 
         if torch.cuda.is_available() and self.params[0].is_cuda:
             mx.set_compute_stream(torch.cuda.current_stream().cuda_stream)
@@ -123,7 +145,9 @@ class ShardedOptimizer:
         # reference, mlsl_impl.cpp:401-411; padding is the flat analog)
         self.shard = (total + self.world - 1) // self.world
         self.flat = torch.zeros(self.shard * self.world, dtype=dt, device=dev)
-        self.flat_grad = torch.zeros_like(self.flat)
+        self._in_place = grads == "in_place" and self.world > 1
+        if not self._in_place:
+            self.flat_grad = torch.zeros_like(self.flat)
         # map parameters onto the flat buffer (they become views)
         off = 0
         with torch.no_grad():
@@ -134,7 +158,8 @@ class ShardedOptimizer:
                 off += n
         lo = self.rank * self.shard
         self.own_param = self.flat[lo:lo + self.shard]
-        self.own_grad = self.flat_grad[lo:lo + self.shard]
+        self.own_grad = (torch.zeros(self.shard, dtype=dt, device=dev) if self._in_place
+                         else self.flat_grad[lo:lo + self.shard])
         # int8 all_gather: the optimizer steps on an exact copy of the shard
         # and flat is the replica everywhere; built once, like _qrs
         self.master = self._delta = self._qag = None
@@ -151,11 +176,34 @@ class ShardedOptimizer:
         self.opt = opt_cls([shard_param], **opt_kwargs)
         # built once: the request owns the error-feedback residual
         self._qrs = None
-        if compression == "int8" and self.world > 1:
+        self._qrs_seg = None
+        self._zero_grads = {}
+        if self._in_place:
+            self._qrs_seg = mx.SegmentedReduceScatter(
+                self.dist, [p.numel() for p in self.params], shard=self.shard,
+                dtype=_dt(self.flat), group=group, algo=rs_algo)
+        elif compression == "int8" and self.world > 1:
             self._qrs = mx.PersistentRequest(self.dist, "reduce_scatter", self.shard,
                                              dtype=_dt(self.flat), op="sum",
                                              group=group, quantized=True,
                                              algo=rs_algo)
+
+    def _grad_list(self):
+        """The gradients as the list request reads them: contiguous, zeros
+        where a parameter has none. The list keeps any copy alive until the
+        request has been waited for."""
+        out = []
+        for i, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                g = self._zero_grads.get(i)
+                if g is None:
+                    g = self._zero_grads[i] = torch.zeros_like(
+                        p.data, memory_format=torch.contiguous_format)
+            else:
+                g = g.detach().contiguous()
+            out.append(g)
+        return out
 
     def _gather_grads(self):
         off = 0
@@ -170,8 +218,15 @@ class ShardedOptimizer:
         self.flat_grad[off:].zero_()
 
     def step(self):
-        self._gather_grads()
-        if self.world > 1:
+        if self._qrs_seg is not None:
+            grads = self._grad_list()
+            self._qrs_seg.start(grads, self.own_grad)
+            self._qrs_seg.wait()
+            del grads
+            if self.average:
+                self.own_grad /= self.world
+        elif self.world > 1:
+            self._gather_grads()
             if self._qrs is not None:
                 # in place: every segment is on the wire before the owned
                 # shard is written
@@ -190,6 +245,7 @@ class ShardedOptimizer:
             if self.average and self.reduce == "rs":
                 self.own_grad /= self.world
         else:
+            self._gather_grads()
             self.own_grad.copy_(self.flat_grad[:self.shard])
 
         self._shard_holder.grad = self.own_grad
