@@ -25,7 +25,16 @@ finish, dequantize_segments at 2, 4 and 8 segments, assigned against
 per-segment and flat dequantize calls and accumulated against dequantize into
 scratch plus reduce_ (--melems elements in all, block 256, f32 and bf16).
 --mode all_gather: quantized all-gather, assign and accumulate, against the
-exact all-gather of --melems elements in all (mp_run.py for N>1)."""
+exact all-gather of --melems elements in all (mp_run.py for N>1).
+--mode int4_kernels: single-GPU A/B of every int4 kernel against its int8
+counterpart (quantize with residual, dequantize, quant_sum_dequant_n and
+quant_sum_requant_n at 4 wires) at --melems Mi elements and at 64 Ki elements,
+f32 and bf16, interleaved rounds; and the f32 quantize4/dequantize4 generic
+against fast kernels from 256 KiB to 16 MiB, which is what the launcher's threshold
+is chosen from.
+--bits4, in the allreduce and reduce_scatter modes: the two-shot or direct
+request also runs with bits=4 (up to 8 ranks), next to its int8 self. --kbytes
+sizes the reduce_scatter's send buffer too, instead of --melems."""
 import argparse
 import json
 import os
@@ -241,6 +250,93 @@ def sum_requant_n(args):
         del own
 
 
+def int4_kernels(args):
+    """One line of JSON per (dtype, size): median and min microseconds of each
+    kernel at 8 and at 4 bits and their ratio; then one line per f32 size of
+    the generic-against-fast A/B. Timing as in sum_dequant_ab."""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("int4_kernels measures GPU kernels: no GPU found")
+    from mlsl_amd import ops
+    torch.cuda.set_device(0)
+    block, nw = 256, 4
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters
+
+    def ab(variants, res):
+        for fn in variants.values():
+            for _ in range(args.warmup):
+                fn()
+        times = {k: [] for k in variants}
+        for _ in range(args.rounds):
+            for k, fn in variants.items():
+                times[k].append(timed(fn))
+        for k, v in times.items():
+            res[f"{k}_us_median"] = round(_median(v) * 1e6, 1)
+            res[f"{k}_us_min"] = round(min(v) * 1e6, 1)
+            res[f"{k}_us_max"] = round(max(v) * 1e6, 1)
+        return {k: _median(v) for k, v in times.items()}
+
+    for dtype, tdt in (("f32", torch.float32), ("bf16", torch.bfloat16)):
+        for count in (args.melems << 20, 64 << 10):
+            torch.manual_seed(0)
+            g = torch.randn(count, dtype=torch.float32, device="cuda").to(tdt)
+            err, out = torch.zeros_like(g), torch.empty_like(g)
+            w8 = [torch.empty(ops.wire_bytes(count, block), dtype=torch.uint8, device="cuda")
+                  for _ in range(nw + 1)]
+            w4 = [torch.empty(ops.wire_bytes(count, block, 4), dtype=torch.uint8,
+                              device="cuda") for _ in range(nw + 1)]
+            for k in range(nw):
+                ops.quantize(g * (k + 1), w8[k], count, block=block, dtype=dtype)
+                ops.quantize4(g * (k + 1), w4[k], count, block=block, dtype=dtype)
+            units = count // block
+            res = {"config": "int4-kernels-ab", "dtype": dtype, "elems": count, "block": block,
+                   "wires": nw, "iters": args.iters, "rounds": args.rounds}
+            med = ab({
+                "quantize8": lambda: ops.quantize(g, w8[nw], count, err=err, block=block,
+                                                  dtype=dtype),
+                "quantize4": lambda: ops.quantize4(g, w4[nw], count, err=err, block=block,
+                                                   dtype=dtype),
+                "dequantize8": lambda: ops.dequantize(w8[0], out, count, block=block,
+                                                      dtype=dtype),
+                "dequantize4": lambda: ops.dequantize4(w4[0], out, count, block=block,
+                                                       dtype=dtype),
+                "sum_dequant_n8": lambda: ops.quant_sum_dequant_n(w8[:nw], out, count,
+                                                                  block=block, dtype=dtype),
+                "sum_dequant_n4": lambda: ops.quant_sum_dequant_n4(w4[:nw], out, count,
+                                                                   block=block, dtype=dtype),
+                "sum_requant_n8": lambda: ops.quant_sum_requant_n(w8[:nw], w8[nw], units,
+                                                                  block=block),
+                "sum_requant_n4": lambda: ops.quant_sum_requant_n4(w4[:nw], w4[nw], units,
+                                                                   block=block),
+            }, res)
+            for k in ("quantize", "dequantize", "sum_dequant_n", "sum_requant_n"):
+                res[f"{k}_4_over_8"] = round(med[k + "4"] / med[k + "8"], 3)
+            print(json.dumps(res), flush=True)
+            del g, err, out, w8, w4
+    for kib in (256, 1024, 2048, 4096, 8192, 16384):
+        count = (kib << 10) // 4
+        g = torch.randn(count, dtype=torch.float32, device="cuda")
+        err, out = torch.zeros_like(g), torch.empty_like(g)
+        wire = torch.empty(ops.wire_bytes(count, block, 4), dtype=torch.uint8, device="cuda")
+        ops.quantize4(g, wire, count, block=block)
+        res = {"config": "int4-f32-path-ab", "kib": kib, "iters": args.iters,
+               "rounds": args.rounds}
+        med = ab({f"{op}_{path}": (lambda op=op, path=path: (
+            ops.quantize4(g, wire, count, err=err, block=block, path=path) if op == "quantize"
+            else ops.dequantize4(wire, out, count, block=block, path=path)))
+            for op in ("quantize", "dequantize") for path in ("generic", "fast")}, res)
+        for op in ("quantize", "dequantize"):
+            res[f"{op}_fast_over_generic"] = round(med[op + "_fast"] / med[op + "_generic"], 3)
+        print(json.dumps(res), flush=True)
+
+
 def dequant_segments_ab(args):
     """One line of JSON per (nseg, dtype): the segmented dequantize of the
     quantized all-gather against what the unchanged kernels offer, --melems
@@ -406,7 +502,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="allreduce",
                     choices=["allreduce", "reduce_scatter", "all_gather", "sum_dequant_ab",
-                             "sum_dequant_n_ab", "dequant_segments_ab", "sum_requant_n"])
+                             "sum_dequant_n_ab", "dequant_segments_ab", "sum_requant_n",
+                             "int4_kernels"])
     ap.add_argument("--exact-only", action="store_true",
                     help="all_gather mode: time the exact request alone")
     ap.add_argument("--melems", type=int, default=64,
@@ -414,7 +511,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--mbytes", type=int, default=256)
     ap.add_argument("--kbytes", type=int, default=0,
-                    help="allreduce mode: message size in KiB instead of --mbytes")
+                    help="message size in KiB instead of --mbytes (allreduce) or --melems "
+                         "(reduce_scatter)")
+    ap.add_argument("--bits4", action="store_true",
+                    help="allreduce and reduce_scatter modes: also time the bits=4 request")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -428,6 +528,8 @@ def main():
         return dequant_segments_ab(args)
     if args.mode == "sum_requant_n":
         return sum_requant_n(args)
+    if args.mode == "int4_kernels":
+        return int4_kernels(args)
     if args.mode == "all_gather":
         return all_gather_bench(args)
     rs = args.mode == "reduce_scatter"
@@ -452,7 +554,7 @@ def main():
     count = nbytes // es
     if rs:
         # `count` stays the send buffer's length; every rank receives 1/size
-        count = (args.melems << 20) // size * size
+        count = (nbytes // es if args.kbytes else args.melems << 20) // size * size
 
     if use_cuda:
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)) %
@@ -488,6 +590,11 @@ def main():
     elif size <= 8:
         dreq = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype, op="sum",
                                     group="data", quantized=True, ar_algo="two_shot")
+    # the same algorithm on the int4 wire
+    req4 = None
+    if args.bits4 and size <= 8:
+        req4 = mx.PersistentRequest(d, kind, req_count, dtype=args.dtype, op="sum",
+                                    group="data", quantized=True, bits=4)
     if rs:
         out_q, out_x = out_q[:req_count], out_x[:req_count]
 
@@ -504,6 +611,9 @@ def main():
     if dreq is not None:
         out_d = out_q.clone() if use_cuda else out_q.copy()
         todo.insert(1, ("quantized_direct" if rs else "quantized_two_shot", dreq, out_d))
+    if req4 is not None:
+        out_4 = out_q.clone() if use_cuda else out_q.copy()
+        todo.insert(len(todo) - 1, ("int4_direct" if rs else "int4_two_shot", req4, out_4))
     for name, req, out in todo:
         for _ in range(args.warmup):
             run(req, out)
@@ -532,6 +642,10 @@ def main():
         if dreq is not None and not rs:
             extra["two_shot_max_abs_err"] = round(float(np.abs(out_d - out_x).max()), 6)
 
+    if req4 is not None:
+        d4 = out_4.float() - out_x.float() if use_cuda else out_4 - out_x
+        extra["int4_max_abs_err"] = round(float(abs(d4).max()), 6)
+        req4.destroy()
     if rank == 0:
         print(json.dumps({
             "config": "int8-quantized-reduce-scatter" if rs

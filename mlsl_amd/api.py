@@ -385,8 +385,17 @@ class PersistentRequest:
     at construction, start/wait/test are allocation-free."""
 
     def __init__(self, dist, kind, count, dtype="f32", op="sum", group="global",
-                 quantized=False, algo=None, accumulate=False, ar_algo=None):
-        """algo: quantized reduce_scatter only. None takes MLSL_QUANT_RS_ALGO
+                 quantized=False, algo=None, accumulate=False, ar_algo=None, bits=8):
+        """bits: the payload bits per element of a quantized request's wire.
+        8 is the int8 wire. 4 is the int4 wire (a block of `set_quant_params`
+        elements, a multiple of 8, takes block/2 + 8 bytes where int8 takes
+        block + 8), for kind="all_reduce" and kind="reduce_scatter" only: a
+        request that names no algorithm then runs two_shot or direct,
+        whatever MLSL_QUANT_AR_ALGO and MLSL_QUANT_RS_ALGO say (those choose
+        between int8 algorithms), and naming "ring" is refused, as are more
+        than 8 ranks and a compression plugin. See
+        mlsl_persistent_all_reduce_quantized_bits.
+        algo: quantized reduce_scatter only. None takes MLSL_QUANT_RS_ALGO
         (ring unless set); "ring" or "direct" names it. See
         mlsl_persistent_reduce_scatter_quantized_algo.
         accumulate: quantized all_gather only. False assigns recv =
@@ -403,6 +412,16 @@ class PersistentRequest:
             raise ValueError('accumulate=True is the accumulating finish of the '
                              'quantized all_gather: it needs kind="all_gather" and '
                              'quantized=True')
+        if bits not in (4, 8):
+            raise ValueError(f"bits={bits!r}: a quantized wire has 4 or 8 payload bits "
+                             "per element")
+        if bits != 8 and not quantized:
+            raise ValueError("bits= names the quantized wire's payload: it needs "
+                             "quantized=True")
+        if bits == 4 and kind not in ("all_reduce", "reduce_scatter"):
+            raise ValueError(f'bits=4 is not wired to kind="{kind}": the 4-bit wire codec '
+                             'serves kind="all_reduce" (two_shot) and '
+                             'kind="reduce_scatter" (direct) only')
         if quantized and kind == "all_to_all":
             raise ValueError('quantized=True is not supported for kind="all_to_all"')
         if algo is not None:
@@ -428,6 +447,11 @@ class PersistentRequest:
             L.mlsl_persistent_all_reduce_quantized_algo.restype = c_int
             L.mlsl_persistent_all_reduce.argtypes = [c_void_p, c_size_t, c_int, c_int,
                                                      c_int, c_int, P(c_void_p)]
+            for n in ("mlsl_persistent_all_reduce_quantized_bits",
+                      "mlsl_persistent_reduce_scatter_quantized_bits"):
+                getattr(L, n).argtypes = [c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                          c_int, P(c_void_p)]
+                getattr(L, n).restype = c_int
             L.mlsl_persistent_reduce_scatter.argtypes = [c_void_p, c_size_t, c_int,
                                                          c_int, c_int, P(c_void_p)]
             L.mlsl_persistent_reduce_scatter_quantized.argtypes = [
@@ -453,7 +477,16 @@ class PersistentRequest:
                 getattr(L, n).restype = c_int
             L._persist_declared = True
         h = c_void_p()
-        if kind == "all_reduce" and ar_algo is not None:
+        if bits == 4:
+            # the int4 wire: two_shot / direct unless named; "ring" raises
+            named, table, fn = ((ar_algo, QUANT_AR_ALGO,
+                                 L.mlsl_persistent_all_reduce_quantized_bits)
+                                if kind == "all_reduce" else
+                                (algo, QUANT_RS_ALGO,
+                                 L.mlsl_persistent_reduce_scatter_quantized_bits))
+            check(fn(dist._h, count, DTYPE[dtype], REDOP[op], GROUP[group],
+                     -1 if named is None else table[named], bits, ctypes.byref(h)))
+        elif kind == "all_reduce" and ar_algo is not None:
             # "ring" requantizes a segment on each of its N-1 reduce hops;
             # "two_shot" sends it to its owner, which sums N wires and
             # requantizes once (at most 8 ranks, no compression plugin, N-1

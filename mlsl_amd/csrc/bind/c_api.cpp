@@ -270,6 +270,56 @@ int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
     C_CATCH
 }
 
+int mlsl_persistent_all_reduce_quantized_bits(mlsl_distribution d, size_t count,
+                                              mlsl_data_type dt, mlsl_reduction op,
+                                              mlsl_group g, int algo, int bits,
+                                              mlsl_request* out) {
+    C_TRY
+    MLSL_CHECK(ROP(op) == ReduceOp::SUM,
+               "quantized all_reduce supports the SUM reduction only");
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized all_reduce supports f32/bf16 only");
+    MLSL_CHECK(algo >= -1 && algo <= 1, "unknown quantized all_reduce algorithm");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddAllReduce(count, ROP(op));
+    // the environment's block size, this request's payload bits
+    QuantParams qp = Environment::GetEnv().GetQuantizationParams();
+    qp.bits = bits;
+    r->SetCompression(Compression::QUANT_INT8, qp);
+    // -1 names no algorithm: two-shot at 4 bits, MLSL_QUANT_AR_ALGO at 8
+    if (algo >= 0)
+        r->SetQuantArAlgo(algo == 1 ? QuantArAlgo::TWO_SHOT : QuantArAlgo::RING);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
+int mlsl_persistent_reduce_scatter_quantized_bits(mlsl_distribution d, size_t recv_count,
+                                                  mlsl_data_type dt, mlsl_reduction op,
+                                                  mlsl_group g, int algo, int bits,
+                                                  mlsl_request* out) {
+    C_TRY
+    MLSL_CHECK(ROP(op) == ReduceOp::SUM,
+               "quantized reduce_scatter supports the SUM reduction only");
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized reduce_scatter supports f32/bf16 only");
+    MLSL_CHECK(algo >= -1 && algo <= 1, "unknown quantized reduce_scatter algorithm");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddReduceScatter(recv_count, ROP(op));
+    // the environment's block size, this request's payload bits
+    QuantParams qp = Environment::GetEnv().GetQuantizationParams();
+    qp.bits = bits;
+    r->SetCompression(Compression::QUANT_INT8, qp);
+    // -1 names no algorithm: direct at 4 bits, MLSL_QUANT_RS_ALGO at 8
+    if (algo >= 0)
+        r->SetQuantRsAlgo(algo == 1 ? QuantRsAlgo::DIRECT : QuantRsAlgo::RING);
+    else if (bits == 8)
+        r->SetQuantRsAlgo(GlobalConfig().quant_rs_algo);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
 int mlsl_persistent_all_reduce_quantized_segments(mlsl_distribution d, const size_t* counts,
                                                   size_t nseg, mlsl_data_type dt,
                                                   mlsl_group g, int algo, float post_scale,

@@ -148,6 +148,71 @@ int mlsl_hip_quant_sum_requant_n(const void* const* wires, int nwires, void* dst
     OPS_CATCH
 }
 
+// The int4 codec. path: 0 lets the launcher choose, 1 names the generic
+// kernel, 2 the fast one (an error where it does not apply).
+int mlsl_hip_quantize4(const void* in, void* err, void* wire, size_t count, size_t block,
+                       int dt, int use_err, int path) {
+    OPS_TRY LaunchQuantize4(in, err, wire, count, block, static_cast<DataType>(dt),
+                            use_err != 0, nullptr, static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_dequantize4(const void* wire, void* out, size_t count, size_t block, int dt,
+                         int path) {
+    OPS_TRY LaunchDequantize4(wire, out, count, block, static_cast<DataType>(dt), nullptr,
+                              static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_quant_sum_dequant_n4(const void* const* wires, int nwires, void* out,
+                                  size_t count, size_t block, int dt, int path) {
+    OPS_TRY LaunchQuantSumDequantN4(wires, nwires, out, count, block,
+                                    static_cast<DataType>(dt), nullptr,
+                                    static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_quant_sum_requant_n4(const void* const* wires, int nwires, void* dst_wire,
+                                  size_t nunits, size_t block, int path) {
+    OPS_TRY LaunchQuantSumRequantN4(wires, nwires, dst_wire, nunits, block, nullptr,
+                                    static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_quant4_blocks_per_trip(int fast, size_t* out) {
+    OPS_TRY* out = Quant4BlocksPerTrip(fast != 0);
+    OPS_CATCH
+}
+
+int mlsl_host_quantize4(const void* in, void* err, void* wire, size_t count, size_t block,
+                        int dt, int use_err) {
+    OPS_TRY HostQuantize(in, err, wire, count, block, static_cast<DataType>(dt), use_err != 0,
+                         4);
+    OPS_CATCH
+}
+
+int mlsl_host_dequantize4(const void* wire, void* out, size_t count, size_t block, int dt) {
+    OPS_TRY HostDequantize(wire, out, count, block, static_cast<DataType>(dt), 4);
+    OPS_CATCH
+}
+
+int mlsl_host_quant_sum_dequant_n4(const void* const* wires, int nwires, void* out,
+                                   size_t count, size_t block, int dt) {
+    OPS_TRY HostQuantSumDequantN(wires, nwires, out, count, block, static_cast<DataType>(dt),
+                                 4);
+    OPS_CATCH
+}
+
+int mlsl_host_quant_sum_requant_n4(const void* const* wires, int nwires, void* dst_wire,
+                                   size_t nunits, size_t block) {
+    OPS_TRY HostQuantSumRequantN(wires, nwires, dst_wire, nunits, block, 4);
+    OPS_CATCH
+}
+
 int mlsl_hip_dequantize_segments(const void* wire, size_t nseg, void* out, size_t count,
                                  size_t block, int dt, int accumulate) {
     OPS_TRY LaunchDequantizeSegments(wire, nseg, out, count, block,

@@ -671,18 +671,25 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
                                  base + p.send_seg * p.seg_wire, p.count, p.block, dt,
                                  p.residual, s);
     } else {
-        for (size_t j = 0; j < p.nseg; ++j)
-            LaunchQuantize(sbuf + j * p.seg_bytes,
-                           p.residual ? base + p.err_off + j * p.seg_bytes : nullptr,
-                           base + (p.send_seg + j) * p.seg_wire, p.count, p.block, dt,
-                           p.residual, s);
+        // p.bits == 4: the int4 codec (flat two-shot allreduce and direct
+        // reduce-scatter only; Setup() refused everything else)
+        for (size_t j = 0; j < p.nseg; ++j) {
+            const uint8_t* in = sbuf + j * p.seg_bytes;
+            uint8_t* err = p.residual ? base + p.err_off + j * p.seg_bytes : nullptr;
+            uint8_t* wire = base + (p.send_seg + j) * p.seg_wire;
+            if (p.bits == 4) LaunchQuantize4(in, err, wire, p.count, p.block, dt, p.residual, s);
+            else LaunchQuantize(in, err, wire, p.count, p.block, dt, p.residual, s);
+        }
     }
     walk(base, base + p.scratch_off);
     const void* wires[kQuantRsDirectMaxRanks];
     FinishWires(p, base, wires);
     switch (p.finish) {
         case QuantFinish::SUMN:
-            LaunchQuantSumDequantN(wires, p.nwires, rbuf, p.count, p.block, dt, s);
+            if (p.bits == 4)
+                LaunchQuantSumDequantN4(wires, p.nwires, rbuf, p.count, p.block, dt, s);
+            else
+                LaunchQuantSumDequantN(wires, p.nwires, rbuf, p.count, p.block, dt, s);
             break;
         case QuantFinish::SUM2:
             LaunchQuantSumDequant(wires[0], wires[1], rbuf, p.count, p.block, dt, s);
@@ -692,6 +699,8 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
                 // round_first: the flat request's bits, then scaled
                 LaunchDequantizeScatter(wires[0], seg_ptrs, seg_offs, nseg, p.count, p.block,
                                         dt, req->PostScale(), /*round_first=*/true, s);
+            else if (p.bits == 4)
+                LaunchDequantize4(wires[0], rbuf, p.count, p.block, dt, s);
             else
                 LaunchDequantize(wires[0], rbuf, p.count, p.block, dt, s);
             break;

@@ -35,8 +35,12 @@ inline void LaunchLocalOp(const Step& st, uint8_t* dst, uint8_t* src, const Quan
     } else if (st.local == Step::LocalOp::SUMQ) {
         const void* wires[kQuantRsDirectMaxRanks];
         SumqWires(plan, plan_base, wires);
-        LaunchQuantSumRequantN(wires, plan.sumq_nwires, plan_base + plan.sumq_dst_off,
-                               plan.sumq_units, plan.block, s);
+        if (plan.bits == 4)
+            LaunchQuantSumRequantN4(wires, plan.sumq_nwires, plan_base + plan.sumq_dst_off,
+                                    plan.sumq_units, plan.block, s);
+        else
+            LaunchQuantSumRequantN(wires, plan.sumq_nwires, plan_base + plan.sumq_dst_off,
+                                   plan.sumq_units, plan.block, s);
     } else if (plan.block > 0) {
         LaunchQuantAccum(dst, src, (st.local_dst.bytes / wire_unit) * plan.block, plan.block, s);
     } else {

@@ -38,74 +38,100 @@ constexpr int kMaxSumWires = 8;
 
 // The requantizing half of the codec, shared by every function that writes a
 // wire block (the device side is QScale / QRound in hip/kernels.hip).
-inline float BlockScale(float block_max) { return block_max > 0.f ? block_max / 127.f : 1.f; }
-inline float QuantRound(float v, float inv_scale) {
-    return std::min(127.f, std::max(-127.f, std::nearbyint(v * inv_scale)));
+// qmax: 127 for the int8 wire, 7 for the int4 one.
+inline float BlockScale(float block_max, float qmax = 127.f) {
+    return block_max > 0.f ? block_max / qmax : 1.f;
+}
+inline float QuantRound(float v, float inv_scale, float qmax = 127.f) {
+    return std::min(qmax, std::max(-qmax, std::nearbyint(v * inv_scale)));
+}
+inline float QMax(int bits) { return bits == 4 ? 7.f : 127.f; }
+inline size_t WireBlock(size_t block, int bits) { return block * bits / 8 + kWireHdr; }
+
+// Element i of a payload: a byte, or at 4 bits nibble i & 1 of byte i >> 1
+// (low nibble first), two's complement.
+inline int PayloadGet(const uint8_t* payload, size_t i, int bits) {
+    if (bits == 8) return static_cast<int8_t>(payload[i]);
+    const int nib = (payload[i >> 1] >> (4 * (i & 1))) & 0xf;
+    return (nib ^ 8) - 8;
+}
+// Into a payload that was zeroed first (the 4-bit store only ORs).
+inline void PayloadPut(uint8_t* payload, size_t i, float q, int bits) {
+    const uint32_t v = static_cast<uint32_t>(static_cast<int32_t>(q));
+    if (bits == 8) payload[i] = static_cast<uint8_t>(v);
+    else payload[i >> 1] |= static_cast<uint8_t>((v & 0xf) << (4 * (i & 1)));
 }
 
 template <typename LOAD, typename STORE>
 void QuantizeImpl(LOAD load, STORE store, void* wire, size_t count, size_t block,
-                  bool use_err) {
+                  bool use_err, int bits = 8) {
     const size_t nblocks = (count + block - 1) / block;
+    const float qmax = QMax(bits);
     uint8_t* w = static_cast<uint8_t*>(wire);
     for (size_t b = 0; b < nblocks; ++b) {
         const size_t base = b * block;
         const size_t n = std::min(block, count - base);
-        uint8_t* wb = w + b * (block + 8);
+        uint8_t* wb = w + b * WireBlock(block, bits);
         float* hdr = reinterpret_cast<float*>(wb);
-        int8_t* payload = reinterpret_cast<int8_t*>(wb + 8);
+        uint8_t* payload = wb + kWireHdr;
         float m = 0.f;
         for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(load(base + i, use_err)));
-        const float scale = BlockScale(m);
+        const float scale = BlockScale(m, qmax);
         hdr[0] = scale;
         hdr[1] = 0.f;
         const float inv = 1.f / scale;
+        // zero first: the padding past n, and what the 4-bit store ORs into
+        std::memset(payload, 0, WireBlock(block, bits) - kWireHdr);
         for (size_t i = 0; i < n; ++i) {
             float v = load(base + i, use_err);
-            const float q = QuantRound(v, inv);
-            payload[i] = static_cast<int8_t>(q);
-            if (use_err) store(base + i, v - q * scale);
+            const float q = QuantRound(v, inv, qmax);
+            PayloadPut(payload, i, q, bits);
+            // the int4 kernels compute the residual with one explicit fma
+            if (use_err) store(base + i, bits == 4 ? std::fmaf(-q, scale, v) : v - q * scale);
         }
-        for (size_t i = n; i < block; ++i) payload[i] = 0;
     }
 }
 
 }  // namespace
 
 void HostQuantize(const void* in, void* err, void* wire, size_t count, size_t block,
-                  DataType dt, bool use_err) {
+                  DataType dt, bool use_err, int bits) {
+    CheckQuantBlock(block, "HostQuantize", bits);
     if (dt == DataType::F32) {
         const float* p = static_cast<const float*>(in);
         float* e = static_cast<float*>(err);
         QuantizeImpl(
             [&](size_t i, bool ue) { return ue ? p[i] + e[i] : p[i]; },
-            [&](size_t i, float v) { e[i] = v; }, wire, count, block, use_err);
+            [&](size_t i, float v) { e[i] = v; }, wire, count, block, use_err, bits);
     } else if (dt == DataType::BF16) {
         const uint16_t* p = static_cast<const uint16_t*>(in);
         uint16_t* e = static_cast<uint16_t*>(err);
         QuantizeImpl(
             [&](size_t i, bool ue) { return ue ? Bf16F(p[i]) + Bf16F(e[i]) : Bf16F(p[i]); },
-            [&](size_t i, float v) { e[i] = F32B(v); }, wire, count, block, use_err);
+            [&](size_t i, float v) { e[i] = F32B(v); }, wire, count, block, use_err, bits);
     } else {
         MLSL_THROW("quantization supports f32/bf16 only");
     }
 }
 
-void HostDequantize(const void* wire, void* out, size_t count, size_t block, DataType dt) {
+void HostDequantize(const void* wire, void* out, size_t count, size_t block, DataType dt,
+                    int bits) {
+    CheckQuantBlock(block, "HostDequantize", bits);
     const size_t nblocks = (count + block - 1) / block;
     const uint8_t* w = static_cast<const uint8_t*>(wire);
     for (size_t b = 0; b < nblocks; ++b) {
         const size_t base = b * block;
         const size_t n = std::min(block, count - base);
-        const uint8_t* wb = w + b * (block + 8);
+        const uint8_t* wb = w + b * WireBlock(block, bits);
         const float scale = reinterpret_cast<const float*>(wb)[0];
-        const int8_t* payload = reinterpret_cast<const int8_t*>(wb + 8);
+        const uint8_t* payload = wb + kWireHdr;
         if (dt == DataType::F32) {
             float* o = static_cast<float*>(out);
-            for (size_t i = 0; i < n; ++i) o[base + i] = payload[i] * scale;
+            for (size_t i = 0; i < n; ++i) o[base + i] = PayloadGet(payload, i, bits) * scale;
         } else if (dt == DataType::BF16) {
             uint16_t* o = static_cast<uint16_t*>(out);
-            for (size_t i = 0; i < n; ++i) o[base + i] = F32B(payload[i] * scale);
+            for (size_t i = 0; i < n; ++i)
+                o[base + i] = F32B(PayloadGet(payload, i, bits) * scale);
         } else {
             MLSL_THROW("dequantization supports f32/bf16 only");
         }
@@ -168,8 +194,8 @@ void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
 }
 
 void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
-                          size_t block, DataType dt) {
-    CheckQuantBlock(block, "HostQuantSumDequantN");
+                          size_t block, DataType dt, int bits) {
+    CheckQuantBlock(block, "HostQuantSumDequantN", bits);
     if (dt != DataType::F32 && dt != DataType::BF16)
         MLSL_THROW("quantized sum-dequantize supports f32/bf16 only");
     MLSL_CHECK(nwires >= 1 && nwires <= 8, "quantized sum-dequantize takes 1 to 8 wires");
@@ -180,17 +206,18 @@ void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_
         const size_t base = blk * block;
         const size_t n = std::min(block, count - base);
         float s[8];
-        const int8_t* p[8];
+        const uint8_t* p[8];
         for (int r = 0; r < nwires; ++r) {
-            const uint8_t* wb = static_cast<const uint8_t*>(wires[r]) + blk * (block + 8);
+            const uint8_t* wb =
+                static_cast<const uint8_t*>(wires[r]) + blk * WireBlock(block, bits);
             std::memcpy(&s[r], wb, 4);
-            p[r] = reinterpret_cast<const int8_t*>(wb + 8);
+            p[r] = wb + kWireHdr;
         }
         for (size_t i = 0; i < n; ++i) {
             // wire order, one explicit fma per wire: the device kernel's bits
             float acc = 0.f;
             for (int r = 0; r < nwires; ++r)
-                acc = std::fmaf(static_cast<float>(p[r][i]), s[r], acc);
+                acc = std::fmaf(static_cast<float>(PayloadGet(p[r], i, bits)), s[r], acc);
             if (dt == DataType::F32) static_cast<float*>(out)[base + i] = acc;
             else static_cast<uint16_t*>(out)[base + i] = F32B(acc);
         }
@@ -198,8 +225,10 @@ void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_
 }
 
 void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
-                          size_t nunits, size_t block) {
-    CheckQuantBlock(block, "HostQuantSumRequantN");
+                          size_t nunits, size_t block, int bits) {
+    CheckQuantBlock(block, "HostQuantSumRequantN", bits);
+    const float qmax = QMax(bits);
+    const size_t unit = WireBlock(block, bits);
     MLSL_CHECK(nwires >= 1 && nwires <= kMaxSumWires,
                "quantized sum-requantize takes 1 to 8 wires");
     MLSL_CHECK(dst_wire != nullptr, "quantized sum-requantize: null destination");
@@ -210,26 +239,27 @@ void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
     std::vector<float> acc(block);
     for (size_t blk = 0; blk < nunits; ++blk) {
         float s[kMaxSumWires];
-        const int8_t* p[kMaxSumWires];
+        const uint8_t* p[kMaxSumWires];
         for (int r = 0; r < nwires; ++r) {
-            const uint8_t* wb = static_cast<const uint8_t*>(wires[r]) + blk * (block + kWireHdr);
+            const uint8_t* wb = static_cast<const uint8_t*>(wires[r]) + blk * unit;
             std::memcpy(&s[r], wb, 4);
-            p[r] = reinterpret_cast<const int8_t*>(wb + kWireHdr);
+            p[r] = wb + kWireHdr;
         }
         float m = 0.f;
         for (size_t i = 0; i < block; ++i) {
             // wire order, one explicit fma per wire: the device kernel's bits
             float a = 0.f;
             for (int r = 0; r < nwires; ++r)
-                a = std::fmaf(static_cast<float>(p[r][i]), s[r], a);
+                a = std::fmaf(static_cast<float>(PayloadGet(p[r], i, bits)), s[r], a);
             acc[i] = a;
             m = std::max(m, std::fabs(a));
         }
-        const float scale = BlockScale(m);
+        const float scale = BlockScale(m, qmax);
         const float inv = 1.f / scale;
-        uint8_t* db = static_cast<uint8_t*>(dst_wire) + blk * (block + kWireHdr);
-        int8_t* dp = reinterpret_cast<int8_t*>(db + kWireHdr);
-        for (size_t i = 0; i < block; ++i) dp[i] = static_cast<int8_t>(QuantRound(acc[i], inv));
+        uint8_t* db = static_cast<uint8_t*>(dst_wire) + blk * unit;
+        uint8_t* dp = db + kWireHdr;
+        std::memset(dp, 0, unit - kWireHdr);
+        for (size_t i = 0; i < block; ++i) PayloadPut(dp, i, QuantRound(acc[i], inv, qmax), bits);
         const float hdr[2] = {scale, 0.f};
         std::memcpy(db, hdr, kWireHdr);
     }

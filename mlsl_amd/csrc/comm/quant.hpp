@@ -14,15 +14,22 @@
 
 namespace mlsl {
 
-inline size_t QuantWireBytes(size_t count, size_t block) {
-    return ((count + block - 1) / block) * (block + 8);
+inline size_t QuantWireBytes(size_t count, size_t block, int bits = 8) {
+    return ((count + block - 1) / block) * (block * static_cast<size_t>(bits) / 8 + 8);
 }
+
+// The functions below that take `bits` speak the int8 wire at 8 and the int4
+// wire at 4: [f32 scale][f32 0][block / 2 payload bytes], element i in nibble
+// i & 1 of payload byte i >> 1 (low nibble first), 4-bit two's complement;
+// scale = max / 7 or 1, q = clamp(rint(v * (1 / scale)), -7, 7), the residual
+// one fma(-q, scale, v); block a multiple of 8. At 4 bits each is bit for bit
+// its Launch*4 kernel (hip/kernels.hpp).
 
 // in (+ err if non-null) -> wire; err updated to the residual.
 void HostQuantize(const void* in, void* err, void* wire, size_t count,
-                  size_t block, DataType dt, bool use_err);
+                  size_t block, DataType dt, bool use_err, int bits = 8);
 void HostDequantize(const void* wire, void* out, size_t count, size_t block,
-                    DataType dt);
+                    DataType dt, int bits = 8);
 // acc_wire += wire in the compressed domain (dequant-sum-requant per block).
 void HostQuantAccum(void* acc_wire, const void* wire, size_t count, size_t block);
 // out = dequant(a_wire) + dequant(b_wire) in the element type, wires
@@ -34,7 +41,7 @@ void HostQuantSumDequant(const void* a_wire, const void* b_wire, void* out,
 // acc = fmaf(q_r, scale_r, acc) in wire order, bit for bit what
 // LaunchQuantSumDequantN computes.
 void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_t count,
-                          size_t block, DataType dt);
+                          size_t block, DataType dt, int bits = 8);
 // dst_wire = requantize(sum over r of dequant(wires[r])), 1 to 8 wires, over
 // nunits whole wire units: the owner's step of the two-shot quantized
 // allreduce. The sum is HostQuantSumDequantN's in float; the requantize is
@@ -42,7 +49,7 @@ void HostQuantSumDequantN(const void* const* wires, int nwires, void* out, size_
 // second header word 0). dst_wire may be exactly one of the wires, or overlap
 // none. Bit for bit what LaunchQuantSumRequantN computes.
 void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
-                          size_t nunits, size_t block);
+                          size_t nunits, size_t block, int bits = 8);
 // The finish of the quantized all-gather: `wire` holds nseg segment wires of
 // QuantWireBytes(count, block) bytes each, every one on a block grid of its
 // own, and segment j goes to out[j * count, (j + 1) * count): assigned as

@@ -3,13 +3,14 @@
 namespace mlsl {
 
 QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t count,
-                        size_t elem_size, QuantGather gather) {
+                        size_t elem_size, QuantGather gather, int bits) {
     auto al16 = [](size_t x) { return (x + 15) & ~size_t(15); };
     const BufRef& res = sch.result;
     MLSL_CHECK(sch.quant_block > 0 && nseg > 0 && (nseg == 1 || me < nseg),
                "not a compressed chunk's schedule");
     QuantPlan p;
     p.block = sch.quant_block;
+    p.bits = bits;
     p.count = count;
     p.seg_bytes = count * elem_size;
     p.seg_wire = sch.wire_bytes / nseg;

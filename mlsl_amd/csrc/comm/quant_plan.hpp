@@ -59,6 +59,7 @@ enum class QuantGather : uint8_t { NONE, ASSIGN, ACCUMULATE };
 
 struct QuantPlan {
     size_t block = 0, count = 0;       // wire block elems; elements per segment (= result elems)
+    int bits = 8;                      // payload bits per element (the request's): 8 or 4
     size_t nseg = 1;                   // send segments (N for reduce-scatter, else 1)
     size_t send_seg = 0;               // wire segment of send segment 0 (`me` for all-gather)
     bool residual = true;              // the prologue carries an error-feedback residual
@@ -83,7 +84,8 @@ struct QuantPlan {
 // of a reduce-scatter, the output segments of an all-gather, which `gather`
 // marks). Throws where the schedule does not fit a finish.
 QuantPlan MakeQuantPlan(const Schedule& sch, size_t nseg, size_t me, size_t count,
-                        size_t elem_size, QuantGather gather = QuantGather::NONE);
+                        size_t elem_size, QuantGather gather = QuantGather::NONE,
+                        int bits = 8);
 
 // The plan's wire tables as pointers from the chunk base `base`, for the
 // N-way kernels and their host twins: the finish's nwires, the SUMQ step's

@@ -191,6 +191,7 @@ void CommRequest::SetCompression(Compression c, const QuantParams& qp) {
 void CommRequest::SetQuantRsAlgo(QuantRsAlgo a) {
     MLSL_CHECK(!setup_done_, "SetQuantRsAlgo after Setup");
     qrs_algo_ = a;
+    qrs_named_ = true;
 }
 
 void CommRequest::SetQuantArAlgo(QuantArAlgo a) {
@@ -260,7 +261,31 @@ void CommRequest::BuildChunks() {
     const int gr = group_->MyIdx(), gs = group_->Size();
     MLSL_CHECK(group_->IsMember(), "request on a group this rank is not in");
     const size_t es = DtypeSize(dtype_);
+    const bool int4 = comp_ == Compression::QUANT_INT8 && qparams_.bits == 4;
+    // The ring requantizes a partial sum on each of its N-1 hops, and at 4 bits
+    // every requantization loses far more than at 8: the int4 codec runs the two
+    // algorithms built to avoid that, and nothing else.
+    static const char* const kInt4NoRing =
+        "the 4-bit wire codec does not run the ring: the ring requantizes the partial "
+        "sum on each of its N-1 hops, and at 4 bits each requantization loses far more "
+        "than at 8; use two_shot (all_reduce) or direct (reduce_scatter), or name no "
+        "algorithm";
     if (comp_ == Compression::QUANT_INT8) {
+        if (qparams_.bits != 8)
+            CheckQuantBlock(qparams_.block_elems, "quantized request", qparams_.bits);
+        if (int4) {
+            MLSL_CHECK(plugin_ == nullptr,
+                       "the 4-bit wire codec cannot run with a compression plugin (the "
+                       "plugin declares its own wire block); unset lib_path or use bits=8");
+            MLSL_CHECK(spec_.op != CollOp::ALLGATHER && spec_.op != CollOp::ALLGATHERV,
+                       "the 4-bit wire codec is not wired to all_gather; use bits=8");
+            MLSL_CHECK(!Segmented(),
+                       "the 4-bit wire codec is not wired to requests over a tensor list; "
+                       "use bits=8");
+            MLSL_CHECK(Compressed(),
+                       "the 4-bit wire codec serves all_reduce and reduce_scatter sums of "
+                       "f32/bf16 only");
+        }
         // an all-gather that was asked to be quantized is never run exact
         // behind the caller's back
         MLSL_CHECK(spec_.op != CollOp::ALLGATHERV,
@@ -359,14 +384,22 @@ void CommRequest::BuildChunks() {
                     // the ranges are gathered pairwise (schedule.hpp).
                     const size_t blk = qparams_.block_elems;
                     const size_t nblocks = (cnt + blk - 1) / blk;
-                    const QuantArAlgo qar = qar_named_ ? qar_algo_ : cfg.quant_ar_algo;
+                    // (at 4 bits MLSL_QUANT_AR_ALGO is not read: it chooses
+                    // between int8 algorithms)
+                    const QuantArAlgo qar = qar_named_ ? qar_algo_
+                                            : int4     ? QuantArAlgo::TWO_SHOT
+                                                       : cfg.quant_ar_algo;
+                    MLSL_CHECK(!int4 || qar == QuantArAlgo::TWO_SHOT, kInt4NoRing);
                     if (qar == QuantArAlgo::TWO_SHOT) {
                         const std::string from_env =
-                            qar_named_ ? "" : " (chosen by MLSL_QUANT_AR_ALGO=two_shot)";
+                            qar_named_ || int4 ? ""
+                                               : " (chosen by MLSL_QUANT_AR_ALGO=two_shot)";
                         MLSL_CHECK(gs <= kQuantRsDirectMaxRanks,
                                    "two-shot quantized all_reduce supports at most 8 "
-                                   "ranks per group (its requantize takes 8 wires); use "
-                                   "the ring" + from_env);
+                                   "ranks per group (its requantize takes 8 wires); use " +
+                                       std::string(int4 ? "bits=8 with the ring, or a "
+                                                          "smaller group"
+                                                        : "the ring") + from_env);
                         MLSL_CHECK(plugin_ == nullptr,
                                    "two-shot quantized all_reduce cannot run with a "
                                    "compression plugin (the plugin ABI has no N-way "
@@ -407,11 +440,17 @@ void CommRequest::BuildChunks() {
                     // requantized.
                     const size_t blk = qparams_.block_elems;
                     const size_t units = (spec_.count + blk - 1) / blk;
-                    if (qrs_algo_ == QuantRsAlgo::DIRECT) {
+                    // (at 4 bits a request that named no algorithm runs direct)
+                    const QuantRsAlgo qrs =
+                        int4 && !qrs_named_ ? QuantRsAlgo::DIRECT : qrs_algo_;
+                    MLSL_CHECK(!int4 || qrs == QuantRsAlgo::DIRECT, kInt4NoRing);
+                    if (qrs == QuantRsAlgo::DIRECT) {
                         MLSL_CHECK(gs <= kQuantRsDirectMaxRanks,
-                                   "direct quantized reduce_scatter supports at most 8 "
-                                   "ranks per group (its fan-in takes 8 wires); use "
-                                   "the ring");
+                                   std::string("direct quantized reduce_scatter supports at "
+                                               "most 8 ranks per group (its fan-in takes 8 "
+                                               "wires); use ") +
+                                       (int4 ? "bits=8 with the ring, or a smaller group"
+                                             : "the ring"));
                         MLSL_CHECK(plugin_ == nullptr,
                                    "direct quantized reduce_scatter cannot run with a "
                                    "compression plugin (the plugin ABI has no N-way "
@@ -501,7 +540,7 @@ void CommRequest::BuildChunks() {
                                                                      : QuantGather::ASSIGN;
             ce.qplan = MakeQuantPlan(
                 ce.sch, spec_.op == CollOp::ALLREDUCE ? 1 : static_cast<size_t>(gs),
-                static_cast<size_t>(gr), spec_.count, es, gather);
+                static_cast<size_t>(gr), spec_.count, es, gather, qparams_.bits);
         }
         total_tmp_bytes_ += ce.sch.tmp_bytes;
         // Phase byte 0xFF is reserved for edge-sequenced p2p tags (PairTag);
@@ -792,7 +831,7 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                     MLSL_CHECK(rc == 0, "quant plugin compress failed");
                 } else {
                     HostQuantize(seg, seg_err, seg_wire, qp.count, qp.block, dtype_,
-                                 qp.residual);
+                                 qp.residual, qp.bits);
                 }
             }
             ce.prologue_done = true;
@@ -846,7 +885,7 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                             if (qp.sumq_units > 0)
                                 HostQuantSumRequantN(in, qp.sumq_nwires,
                                                      wire + qp.sumq_dst_off, qp.sumq_units,
-                                                     qp.block);
+                                                     qp.block, qp.bits);
                         } else if (ce.sch.quant_block > 0) {
                             const size_t blk = ce.sch.quant_block;
                             const size_t units =
@@ -890,7 +929,7 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                         switch (qp.finish) {
                             case QuantFinish::SUMN:
                                 HostQuantSumDequantN(wires, qp.nwires, rbase, qp.count,
-                                                     qp.block, dtype_);
+                                                     qp.block, dtype_, qp.bits);
                                 break;
                             case QuantFinish::SUM2:
                                 HostQuantSumDequant(wires[0], wires[1], rbase, qp.count,
@@ -906,7 +945,8 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                                                           post_scale_,
                                                           /*round_first=*/true);
                                 else
-                                    HostDequantize(wires[0], rbase, qp.count, qp.block, dtype_);
+                                    HostDequantize(wires[0], rbase, qp.count, qp.block, dtype_,
+                                                   qp.bits);
                                 break;
                             case QuantFinish::SCATTER:
                                 HostDequantizeSegments(wires[0], qp.out_segs, rbase, qp.count,

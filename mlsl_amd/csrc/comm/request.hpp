@@ -129,6 +129,12 @@ class CommRequest {
     // quantization with error feedback, fused into the collective. Call
     // before Setup(); honored for ALLREDUCE and REDUCE_SCATTER with SUM, and
     // for ALLGATHER (no error feedback there), on f32/bf16.
+    // qp.bits == 4 selects the int4 wire codec, wired to the two algorithms that
+    // do not requantize hop by hop: an ALLREDUCE runs TWO_SHOT and a
+    // REDUCE_SCATTER runs DIRECT unless SetQuant*Algo names it, whatever
+    // MLSL_QUANT_AR_ALGO / MLSL_QUANT_RS_ALGO say, and Setup() fails for the ring,
+    // for ALLGATHER, over a tensor list, with a plugin, on more than 8 ranks, for
+    // a block that is no multiple of 8 and for bits other than 4 or 8.
     void SetCompression(Compression c, const QuantParams& qp);
     // Algorithm of a quantized REDUCE_SCATTER (ignored by every other op).
     // Call before Setup(). DIRECT keeps N-1 segment-wires of scratch where
@@ -230,6 +236,7 @@ class CommRequest {
     QuantParams qparams_;
     const struct QuantPluginApi* plugin_ = nullptr;  // dlopen'd compression
     QuantRsAlgo qrs_algo_ = QuantRsAlgo::RING;
+    bool qrs_named_ = false;   // false at 4 bits: direct, whatever the variable says
     bool qag_accumulate_ = false;
     QuantArAlgo qar_algo_ = QuantArAlgo::RING;   // meaningful once qar_named_
     bool qar_named_ = false;   // false: MLSL_QUANT_AR_ALGO decides at Setup()

@@ -125,10 +125,12 @@ struct QuantParams {
     std::string dequant_fn = "dl_comp_decompress_buffer";
     std::string reduce_fn = "dl_comp_compressed_buffer_reduce_sum";
     size_t block_bytes = 0;     // plugin wire-block bytes (0 = derived)
-    // On-wire block: plugin-declared size, else int8 payload + fp32 scale
-    // + fp32 reserved.
+    int bits = 8;               // payload bits per element: 8, or 4 (built-in codec only)
+    // On-wire block: plugin-declared size, else the payload (one byte per
+    // element, or one nibble) + fp32 scale + fp32 reserved.
     size_t WireBlockBytes() const {
-        return block_bytes ? block_bytes : block_elems + 2 * sizeof(float);
+        return block_bytes ? block_bytes
+                           : block_elems * static_cast<size_t>(bits) / 8 + 2 * sizeof(float);
     }
 };
 
@@ -151,11 +153,19 @@ class Error : public std::runtime_error {
 // An int8 wire block is [f32 scale][f32 reserved][int8 x block_elems], one
 // after the other: only a non-zero multiple of 4 keeps every block's header
 // (and the 4-byte payload words of the kernels) naturally aligned.
-inline void CheckQuantBlock(size_t block_elems, const char* where) {
-    if (block_elems == 0 || block_elems % 4 != 0)
+// An int4 wire block is [f32 scale][f32 0][block_elems / 2 payload bytes],
+// element i in nibble i & 1 of payload byte i >> 1: a multiple of 8 makes the
+// payload whole 32-bit words, which the kernels load and store one per lane.
+inline void CheckQuantBlock(size_t block_elems, const char* where, int bits = 8) {
+    if (bits != 4 && bits != 8)
+        throw Error(std::string(where) + ": a quantized payload of " + std::to_string(bits) +
+                    " bits per element is not supported (bits must be 4 or 8)");
+    const size_t mult = bits == 4 ? 8 : 4;
+    if (block_elems == 0 || block_elems % mult != 0)
         throw Error(std::string(where) + ": quantization block of " +
                     std::to_string(block_elems) +
-                    " elements is not supported (must be a non-zero multiple of 4)");
+                    " elements is not supported (must be a non-zero multiple of " +
+                    std::to_string(mult) + (bits == 4 ? " at 4 bits)" : ")"));
 }
 
 }  // namespace mlsl

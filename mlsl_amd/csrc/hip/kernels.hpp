@@ -83,6 +83,40 @@ void LaunchQuantSumDequantN(const void* const* wires, int nwires, void* out, siz
 // read during the call.
 void LaunchQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
                             size_t nunits, size_t block_elems, hipStream_t stream);
+// --- int4 block quantization: the same codec at 4 bits ---
+// Wire block layout: [float scale][float 0][block_elems / 2 payload bytes];
+// element i is nibble i & 1 of payload byte i >> 1 (low nibble first), 4-bit
+// two's complement. scale = max|v| / 7 (1 for an all-zero block),
+// q = clamp(rint(v * (1 / scale)), -7, 7), residual = fma(-q, scale, v);
+// nibbles past `count` in the last block are 0. block_elems is a non-zero
+// multiple of 8 and every wire 4-byte aligned. Each launcher has a generic
+// kernel (any legal block, partial last block, element buffers aligned to the
+// element) and a fast one (block 256, whole blocks, 16-byte aligned element
+// buffers, 8-byte aligned wires); AUTO takes the fast one where it applies
+// (f32 quantize and dequantize from 256 KiB up), GENERIC and FAST name one (FAST
+// throws where it does not apply): the A/B hook. The host twins
+// (comm/quant.hpp, bits = 4) compute the same bits.
+enum class Quant4Path : int { AUTO = 0, GENERIC = 1, FAST = 2 };
+void LaunchQuantize4(const void* in, void* err, void* wire, size_t count,
+                     size_t block_elems, DataType dt, bool use_err, hipStream_t stream,
+                     Quant4Path path = Quant4Path::AUTO);
+void LaunchDequantize4(const void* wire, void* out, size_t count, size_t block_elems,
+                       DataType dt, hipStream_t stream, Quant4Path path = Quant4Path::AUTO);
+// LaunchQuantSumDequantN over int4 wires: the finish of the direct
+// reduce-scatter at 4 bits. The same fma chain in wire order from +0.
+void LaunchQuantSumDequantN4(const void* const* wires, int nwires, void* out, size_t count,
+                             size_t block_elems, DataType dt, hipStream_t stream,
+                             Quant4Path path = Quant4Path::AUTO);
+// LaunchQuantSumRequantN over int4 wires of block_elems / 2 + 8 byte units:
+// the owner's step of the two-shot allreduce at 4 bits. dst_wire may be
+// EXACTLY one of the wires or overlap none. Plain stores.
+void LaunchQuantSumRequantN4(const void* const* wires, int nwires, void* dst_wire,
+                             size_t nunits, size_t block_elems, hipStream_t stream,
+                             Quant4Path path = Quant4Path::AUTO);
+// Wire blocks one launch of an int4 kernel covers before its grid-stride loop
+// takes a second trip (the grid cap; for tests that want to pass it).
+size_t Quant4BlocksPerTrip(bool fast);
+
 // Finish of the quantized all-gather, one launch for any nseg >= 1: `wire`
 // holds nseg segment wires of NumBlocks(count) blocks each, one after the
 // other and every one on a block grid of its own (a partial last block is

@@ -118,6 +118,29 @@ int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
                                               mlsl_data_type dt, mlsl_reduction op,
                                               mlsl_group g, mlsl_quant_ar_algo algo,
                                               mlsl_request* out);
+/* The quantized allreduce and reduce-scatter (sums of f32/bf16) with the
+ * payload bits of their wire named per request. bits == 8 is the int8 wire of
+ * the functions around this one. bits == 4 is the int4 wire: a block is
+ * [f32 scale][f32 0][block / 2 payload bytes], element i in nibble i & 1 of
+ * payload byte i >> 1, scale = max|v| / 7, q in -7..7, block / 2 + 8 bytes
+ * where int8 takes block + 8 (136 against 264 at block 256). The block size
+ * stays mlsl_set_quant_params' and must be a multiple of 8 at 4 bits.
+ * algo: -1 names none, 0 the ring, 1 two-shot (allreduce) or direct
+ * (reduce-scatter). At 4 bits -1 runs two-shot or direct whatever
+ * MLSL_QUANT_AR_ALGO and MLSL_QUANT_RS_ALGO say (they choose between int8
+ * algorithms), and the ring fails at creation: it requantizes on every hop,
+ * which at 4 bits loses far more than at 8. Also failing at creation at 4
+ * bits: a group of more than 8 ranks, a compression plugin, a block that is
+ * no multiple of 8; and any bits other than 4 or 8. The all-gather and the
+ * requests over a tensor list have no 4-bit form. */
+int mlsl_persistent_all_reduce_quantized_bits(mlsl_distribution d, size_t count,
+                                              mlsl_data_type dt, mlsl_reduction op,
+                                              mlsl_group g, int algo, int bits,
+                                              mlsl_request* out);
+int mlsl_persistent_reduce_scatter_quantized_bits(mlsl_distribution d, size_t recv_count,
+                                                  mlsl_data_type dt, mlsl_reduction op,
+                                                  mlsl_group g, int algo, int bits,
+                                                  mlsl_request* out);
 /* The int8-quantized allreduce (a sum) over a LIST of nseg tensors of
  * counts[j] >= 1 elements each, in place: it is the quantized allreduce of
  * their concatenation, which is never built. The quantize prologue reads the

@@ -90,6 +90,17 @@ void LaunchQuantSumRequantN(const void* const* w, int nw, void* dst, size_t unit
     Record("LaunchQuantSumRequantN", nw, dst, units, blk, st);
     for (int k = 0; k < nw; ++k) Record(" wire", w[k]);
 }
+void LaunchQuantize4(const void* in, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st, Quant4Path path) STUB(LaunchQuantize4, in, err, w, n, blk, dt, use_err, st, path)
+void LaunchDequantize4(const void* w, void* out, size_t n, size_t blk, DataType dt, hipStream_t st, Quant4Path path) STUB(LaunchDequantize4, w, out, n, blk, dt, st, path)
+void LaunchQuantSumDequantN4(const void* const* w, int nw, void* out, size_t n, size_t blk, DataType dt, hipStream_t st, Quant4Path path) {
+    Record("LaunchQuantSumDequantN4", nw, out, n, blk, dt, st, path);
+    for (int k = 0; k < nw; ++k) Record(" wire", w[k]);
+}
+void LaunchQuantSumRequantN4(const void* const* w, int nw, void* dst, size_t units, size_t blk, hipStream_t st, Quant4Path path) {
+    Record("LaunchQuantSumRequantN4", nw, dst, units, blk, st, path);
+    for (int k = 0; k < nw; ++k) Record(" wire", w[k]);
+}
+size_t Quant4BlocksPerTrip(bool fast) { return fast ? 16384 : 8192; }
 void LaunchDequantizeSegments(const void* w, size_t nseg, void* out, size_t n, size_t blk, DataType dt, bool acc, hipStream_t st) STUB(LaunchDequantizeSegments, w, nseg, out, n, blk, dt, acc, st)
 void LaunchQuantizeGather(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGather, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st)
 void LaunchQuantizeGatherShards(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t total, size_t nshards, size_t shard, size_t stride, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGatherShards, ptrs, offs, nseg, err, w, total, nshards, shard, stride, blk, dt, use_err, st)

@@ -48,6 +48,21 @@ def _lib():
         L.mlsl_host_quant_sum_requant_n.argtypes = L.mlsl_hip_quant_sum_requant_n.argtypes
         L.mlsl_hip_quant_sum_requant_n.restype = c.c_int
         L.mlsl_host_quant_sum_requant_n.restype = c.c_int
+        L.mlsl_hip_quantize4.argtypes = L.mlsl_hip_quantize.argtypes + [c.c_int]
+        L.mlsl_hip_dequantize4.argtypes = L.mlsl_hip_dequantize.argtypes + [c.c_int]
+        L.mlsl_hip_quant_sum_dequant_n4.argtypes = \
+            L.mlsl_hip_quant_sum_dequant_n.argtypes + [c.c_int]
+        L.mlsl_hip_quant_sum_requant_n4.argtypes = \
+            L.mlsl_hip_quant_sum_requant_n.argtypes + [c.c_int]
+        L.mlsl_hip_quant4_blocks_per_trip.argtypes = [c.c_int, c.POINTER(c.c_size_t)]
+        L.mlsl_host_quantize4.argtypes = L.mlsl_hip_quantize.argtypes
+        L.mlsl_host_dequantize4.argtypes = L.mlsl_hip_dequantize.argtypes
+        L.mlsl_host_quant_sum_dequant_n4.argtypes = L.mlsl_hip_quant_sum_dequant_n.argtypes
+        L.mlsl_host_quant_sum_requant_n4.argtypes = L.mlsl_hip_quant_sum_requant_n.argtypes
+        for n in ("quantize4", "dequantize4", "quant_sum_dequant_n4", "quant_sum_requant_n4"):
+            getattr(L, "mlsl_hip_" + n).restype = c.c_int
+            getattr(L, "mlsl_host_" + n).restype = c.c_int
+        L.mlsl_hip_quant4_blocks_per_trip.restype = c.c_int
         L.mlsl_hip_dequantize_segments.argtypes = [c.c_void_p, c.c_size_t, c.c_void_p,
                                                    c.c_size_t, c.c_size_t, c.c_int, c.c_int]
         L.mlsl_host_dequantize_segments.argtypes = L.mlsl_hip_dequantize_segments.argtypes
@@ -151,10 +166,73 @@ def copy_variant(dst, src, bytes_, nt):
     check(_lib().mlsl_hip_copy_variant(dp, sp, bytes_, 1 if nt else 0))
 
 
-def wire_bytes(count, block=256):
-    """Bytes of the int8 wire format for `count` elements."""
+def wire_bytes(count, block=256, bits=8):
+    """Bytes of the wire format for `count` elements: int8 (bits=8) or int4
+    (bits=4) payload after each block's 8-byte header."""
     nblocks = (count + block - 1) // block
-    return nblocks * (block + 8)
+    return nblocks * (block * bits // 8 + 8)
+
+
+_PATH4 = {None: 0, "generic": 1, "fast": 2}
+
+
+def _check_block4(block):
+    if block == 0 or block % 8:
+        raise ValueError(f"quantization block of {block} elements is not supported "
+                         "(must be a non-zero multiple of 8 at 4 bits)")
+
+
+def quant4_blocks_per_trip(fast):
+    """Wire blocks one launch of an int4 kernel covers before its grid-stride
+    loop takes a second trip, on the fast or the generic path."""
+    n = ctypes.c_size_t(0)
+    check(_lib().mlsl_hip_quant4_blocks_per_trip(1 if fast else 0, ctypes.byref(n)))
+    return n.value
+
+
+def quantize4(inp, wire, count, err=None, block=256, dtype=None, path=None):
+    """`quantize` into the int4 wire: [f32 scale][f32 0][block/2 bytes] per
+    block, element i in nibble i & 1 of payload byte i >> 1, scale = max/7,
+    q in -7..7; `err`, if given, is added to the input and left holding the
+    residual fma(-q, scale, v). block is a multiple of 8. path=None lets the
+    launcher choose its kernel, "generic" or "fast" names it (the A/B hook;
+    "fast" needs block 256, whole blocks and aligned buffers)."""
+    _check_block4(block)
+    ip, d1 = _as_ptr_dtype(inp)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize4(ip, ep, wp, count, block, DTYPE[dtype or d1],
+                                    1 if err is not None else 0, _PATH4[path]))
+
+
+def dequantize4(wire, out, count, block=256, dtype=None, path=None):
+    """`dequantize` of an int4 wire (see `quantize4`)."""
+    _check_block4(block)
+    wp, _ = _as_ptr_dtype(wire)
+    op_, d1 = _as_ptr_dtype(out)
+    check(_lib().mlsl_hip_dequantize4(wp, op_, count, block, DTYPE[dtype or d1],
+                                      _PATH4[path]))
+
+
+def quant_sum_dequant_n4(wires, out, count, block=256, dtype=None, path=None):
+    """`quant_sum_dequant_n` over int4 wires: the finish of the direct
+    reduce_scatter at bits=4."""
+    _check_block4(block)
+    ptrs = (ctypes.c_void_p * len(wires))(*[_as_ptr_dtype(w)[0].value for w in wires])
+    op_, d1 = _as_ptr_dtype(out)
+    check(_lib().mlsl_hip_quant_sum_dequant_n4(ptrs, len(wires), op_, count, block,
+                                               DTYPE[dtype or d1], _PATH4[path]))
+
+
+def quant_sum_requant_n4(wires, dst, nunits, block=256, path=None):
+    """`quant_sum_requant_n` over int4 wires, units of block/2 + 8 bytes: the
+    owner's step of the two-shot all_reduce at bits=4. `dst` may be exactly
+    one of the wires or overlap none."""
+    _check_block4(block)
+    ptrs = (ctypes.c_void_p * len(wires))(*[_as_ptr_dtype(w)[0].value for w in wires])
+    dp, _ = _as_ptr_dtype(dst)
+    check(_lib().mlsl_hip_quant_sum_requant_n4(ptrs, len(wires), dp, nunits, block,
+                                               _PATH4[path]))
 
 
 def quantize(inp, wire, count, err=None, block=256, dtype=None):
@@ -507,6 +585,46 @@ def host_quant_sum_requant_n(wires, dst, nunits, block=256):
         *[_host_buf(w, need, f"wires[{i}]").value for i, w in enumerate(wires)])
     dp = _host_buf(dst, need, "dst")
     check(_lib().mlsl_host_quant_sum_requant_n(ptrs, len(wires), dp, nunits, block))
+
+
+def host_quantize4(inp, wire, count, err=None, block=256, dtype="f32"):
+    """Host twin of `quantize4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    eb = _ELEM_BYTES[dtype]
+    ip = _host_buf(inp, count * eb, "inp")
+    wp = _host_buf(wire, wire_bytes(count, block, 4), "wire")
+    ep = None if err is None else _host_buf(err, count * eb, "err")
+    check(_lib().mlsl_host_quantize4(ip, ep, wp, count, block, DTYPE[dtype],
+                                     1 if err is not None else 0))
+
+
+def host_dequantize4(wire, out, count, block=256, dtype="f32"):
+    """Host twin of `dequantize4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    wp = _host_buf(wire, wire_bytes(count, block, 4), "wire")
+    op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
+    check(_lib().mlsl_host_dequantize4(wp, op_, count, block, DTYPE[dtype]))
+
+
+def host_quant_sum_dequant_n4(wires, out, count, block=256, dtype="f32"):
+    """Host twin of `quant_sum_dequant_n4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    ptrs = (ctypes.c_void_p * len(wires))(
+        *[_host_buf(w, wire_bytes(count, block, 4), f"wires[{i}]").value
+          for i, w in enumerate(wires)])
+    op_ = _host_buf(out, count * _ELEM_BYTES[dtype], "out")
+    check(_lib().mlsl_host_quant_sum_dequant_n4(ptrs, len(wires), op_, count, block,
+                                                DTYPE[dtype]))
+
+
+def host_quant_sum_requant_n4(wires, dst, nunits, block=256):
+    """Host twin of `quant_sum_requant_n4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    need = nunits * (block // 2 + 8)
+    ptrs = (ctypes.c_void_p * len(wires))(
+        *[_host_buf(w, need, f"wires[{i}]").value for i, w in enumerate(wires)])
+    dp = _host_buf(dst, need, "dst")
+    check(_lib().mlsl_host_quant_sum_requant_n4(ptrs, len(wires), dp, nunits, block))
 
 
 def host_dequantize_segments(wire, out, count, nseg, block=256, dtype="f32",

@@ -80,6 +80,12 @@ class ShardedOptimizer:
         compression: "none", or "int8" for the quantized reduce_scatter
         (needs reduce="rs" and f32 or bf16 parameters; block size from
         mx.set_quant_params). A group of one exchanges nothing either way.
+        "int4" is that reduce_scatter on the 4-bit wire (about half the wire
+        bytes, 15 levels per block instead of 255, the error fed back the
+        same way): PersistentRequest(..., bits=4) on the grads="copy" path.
+        It runs "direct" only: rs_algo may be None or "direct", and "ring"
+        and grads="in_place" are refused (the tensor-list request has no
+        4-bit form); the block size must be a multiple of 8.
         rs_algo: algorithm of that quantized reduce_scatter: None
         (MLSL_QUANT_RS_ALGO, ring unless set), "ring", or "direct" (each shard
         goes straight to its owner and is summed once, nothing requantized;
@@ -105,15 +111,24 @@ class ShardedOptimizer:
         self.average = average
         assert reduce in ("none", "rs")
         self.reduce = reduce
-        if compression not in ("none", "int8"):
-            raise ValueError(f"compression={compression!r}: expected 'none' or 'int8'")
-        if compression == "int8" and reduce != "rs":
-            raise ValueError('compression="int8" compresses the gradient '
+        if compression not in ("none", "int8", "int4"):
+            raise ValueError(f"compression={compression!r}: expected 'none', 'int8' or "
+                             "'int4'")
+        if compression != "none" and reduce != "rs":
+            raise ValueError(f'compression="{compression}" compresses the gradient '
                              'reduce_scatter: it needs reduce="rs"')
+        if compression == "int4" and rs_algo == "ring":
+            raise ValueError('compression="int4" does not run rs_algo="ring": the ring '
+                             'requantizes on every hop, which at 4 bits loses far more than '
+                             'at 8; use rs_algo=None or "direct"')
+        if compression == "int4" and grads == "in_place":
+            raise ValueError('compression="int4" is not wired to grads="in_place" (the '
+                             'reduce_scatter over a tensor list has no 4-bit form); use '
+                             'grads="copy"')
         self.compression = compression
         if rs_algo not in (None, "ring", "direct"):
             raise ValueError(f"rs_algo={rs_algo!r}: expected None, 'ring' or 'direct'")
-        if rs_algo is not None and compression != "int8":
+        if rs_algo is not None and compression == "none":
             raise ValueError('rs_algo= selects the quantized reduce_scatter\'s '
                              'algorithm: it needs compression="int8"')
         self.rs_algo = rs_algo
@@ -136,8 +151,9 @@ class ShardedOptimizer:
         dt = self.params[0].dtype
         assert all(p.dtype == dt for p in self.params), \
             "one flat group: uniform dtype required"
-        if compression == "int8" and dt not in (torch.float32, torch.bfloat16):
-            raise ValueError(f'compression="int8" supports f32/bf16 parameters, not {dt}')
+        if compression != "none" and dt not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'compression="{compression}" supports f32/bf16 parameters, '
+                             f'not {dt}')
         if ag_compression == "int8" and dt not in (torch.float32, torch.bfloat16):
             raise ValueError(f'ag_compression="int8" supports f32/bf16 parameters, not {dt}')
         total = sum(p.numel() for p in self.params)
@@ -182,11 +198,12 @@ class ShardedOptimizer:
             self._qrs_seg = mx.SegmentedReduceScatter(
                 self.dist, [p.numel() for p in self.params], shard=self.shard,
                 dtype=_dt(self.flat), group=group, algo=rs_algo)
-        elif compression == "int8" and self.world > 1:
+        elif compression != "none" and self.world > 1:
             self._qrs = mx.PersistentRequest(self.dist, "reduce_scatter", self.shard,
                                              dtype=_dt(self.flat), op="sum",
                                              group=group, quantized=True,
-                                             algo=rs_algo)
+                                             algo=rs_algo,
+                                             bits=4 if compression == "int4" else 8)
 
     def _grad_list(self):
         """The gradients as the list request reads them: contiguous, zeros
