@@ -176,6 +176,18 @@ $(ASAN_QSEG): mlsl_amd/csrc/tests/quant_seg_selftest.cpp mlsl_amd/csrc/comm/sche
 	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
 	    $^ -pthread -ldl -o $@
 
+# The same at 4 bits: the host twins over exact-size heap tensors at blocks 256
+# and 24, and the two-shot exchange walked by hand for worlds 1 to 8.
+ASAN_QSEG4 := $(BUILD)/quant_seg4_selftest_asan
+
+asan-quant-seg4: $(ASAN_QSEG4)
+	$(ASAN_QSEG4)
+
+$(ASAN_QSEG4): mlsl_amd/csrc/tests/quant_seg4_selftest.cpp mlsl_amd/csrc/comm/schedule.cpp mlsl_amd/csrc/comm/quant.cpp mlsl_amd/csrc/comm/quant_plan.cpp mlsl_amd/csrc/core/log.cpp
+	@mkdir -p $(dir $@)
+	g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer \
+	    $^ -pthread -ldl -o $@
+
 # The reduce-scatter prologue over a list of tensors under ASan/UBSan: the host
 # twin over exact-size heap tensors (padding is read through no pointer), and
 # the ring and direct exchanges walked by hand inside plan-sized buffers into an

@@ -19,6 +19,12 @@ SegmentedAllReduce with post_scale = 1/world. Device events on the compute
 stream bracket each whole sequence (the request is waited for before the
 closing event is recorded).
 
+--bits4 measures the int4 wire instead: gather4 / scatter4 against the flat
+quantize4 / dequantize4 (flat_a, flat_b) and, in the same run on the same
+tensors, against the int8 list kernels (gather8_*, scatter8_*); --path names
+the int4 list kernels' path (fast: one block per half-wave; generic: one wave
+per block). In bucket mode both requests run at 4 bits.
+
 One JSON line per configuration. No GPU: exits with an error."""
 import argparse
 import json
@@ -57,7 +63,16 @@ def kernels(args):
     src = (torch.randn(total, dtype=torch.float32, device="cuda") * 0.01).to(tdt)
     out = torch.empty_like(src)
     err = torch.zeros_like(src)
-    wire = torch.empty(ops.wire_bytes(total, block), dtype=torch.uint8, device="cuda")
+    bits = 4 if args.bits4 else 8
+    wire = torch.empty(ops.wire_bytes(total, block, bits), dtype=torch.uint8, device="cuda")
+    if args.bits4:
+        quantize, dequantize = ops.quantize4, ops.dequantize4
+        gather = lambda *a, **k: ops.quantize_gather4_tables(*a, path=args.path, **k)  # noqa: E731
+        scatter = lambda *a, **k: ops.dequantize_scatter4_tables(*a, path=args.path, **k)  # noqa: E731
+        wire8 = torch.empty(ops.wire_bytes(total, block), dtype=torch.uint8, device="cuda")
+    else:
+        quantize, dequantize = ops.quantize, ops.dequantize
+        gather, scatter = ops.quantize_gather_tables, ops.dequantize_scatter_tables
 
     def tables(counts, base):
         offs = [0]
@@ -70,29 +85,37 @@ def kernels(args):
     layouts = {"aligned64": [total // 64] * 64, "ragged4096": _ragged(total, 4096)}
     variants = {}
     for tag in ("flat_a", "flat_b"):
-        variants[f"quantize_{tag}"] = lambda: ops.quantize(src, wire, total, err=err,
-                                                           block=block, dtype=args.dtype)
-        variants[f"dequantize_{tag}"] = lambda: ops.dequantize(wire, out, total, block=block,
-                                                               dtype=args.dtype)
+        variants[f"quantize_{tag}"] = lambda: quantize(src, wire, total, err=err,
+                                                       block=block, dtype=args.dtype)
+        variants[f"dequantize_{tag}"] = lambda: dequantize(wire, out, total, block=block,
+                                                           dtype=args.dtype)
     for name, counts in layouts.items():
         ip, io, n = tables(counts, src)
         op_, oo, _ = tables(counts, out)
         variants[f"gather_{name}"] = (
-            lambda ip=ip, io=io, n=n: ops.quantize_gather_tables(
+            lambda ip=ip, io=io, n=n: gather(
                 ip, io, n, total, wire, err=err, block=block, dtype=args.dtype))
         variants[f"scatter_{name}"] = (
-            lambda op_=op_, oo=oo, n=n: ops.dequantize_scatter_tables(
+            lambda op_=op_, oo=oo, n=n: scatter(
                 wire, op_, oo, n, total, block=block, dtype=args.dtype, post_scale=0.5))
+        if args.bits4:
+            # the int8 list kernels on the same tensors, a wire of their own
+            variants[f"gather8_{name}"] = (
+                lambda ip=ip, io=io, n=n: ops.quantize_gather_tables(
+                    ip, io, n, total, wire8, err=err, block=block, dtype=args.dtype))
+            variants[f"scatter8_{name}"] = (
+                lambda op_=op_, oo=oo, n=n: ops.dequantize_scatter_tables(
+                    wire8, op_, oo, n, total, block=block, dtype=args.dtype, post_scale=0.5))
 
     # same bits before anything is timed (post_scale 1 for the comparison)
     ref_w, ref_o = torch.empty_like(wire), torch.empty_like(out)
-    ops.quantize(src, ref_w, total, block=block, dtype=args.dtype)
-    ops.dequantize(ref_w, ref_o, total, block=block, dtype=args.dtype)
+    quantize(src, ref_w, total, block=block, dtype=args.dtype)
+    dequantize(ref_w, ref_o, total, block=block, dtype=args.dtype)
     for name, counts in layouts.items():
         ip, io, n = tables(counts, src)
         op_, oo, _ = tables(counts, out)
-        ops.quantize_gather_tables(ip, io, n, total, wire, block=block, dtype=args.dtype)
-        ops.dequantize_scatter_tables(wire, op_, oo, n, total, block=block, dtype=args.dtype)
+        gather(ip, io, n, total, wire, block=block, dtype=args.dtype)
+        scatter(wire, op_, oo, n, total, block=block, dtype=args.dtype)
         assert torch.equal(wire, ref_w) and torch.equal(out.view(torch.uint8),
                                                         ref_o.view(torch.uint8)), name
 
@@ -108,6 +131,8 @@ def kernels(args):
             us += e0.elapsed_time(e1) * 1e3
         return us / args.iters
 
+    if args.bits4:
+        ops.quantize(src, wire8, total, block=block, dtype=args.dtype)   # for scatter8_*
     for fn in variants.values():
         for _ in range(args.warmup):
             fn()
@@ -118,13 +143,16 @@ def kernels(args):
             times[k].append(timed(fn))
     med = {k: _stats(v)["median"] for k, v in times.items()}
     res = {"config": "quant-seg-kernels", "dtype": args.dtype, "total_mib": total * es >> 20,
-           "block": block, "iters": args.iters, "rounds": args.rounds,
-           **{f"{k}_us": _stats(v) for k, v in times.items()}}
+           "block": block, "bits": bits, "path": args.path, "iters": args.iters,
+           "rounds": args.rounds, **{f"{k}_us": _stats(v) for k, v in times.items()}}
     for kind, flat in (("gather", "quantize"), ("scatter", "dequantize")):
         a, b = med[f"{flat}_flat_a"], med[f"{flat}_flat_b"]
         res[f"{flat}_flat_spread"] = round(abs(a - b) / min(a, b), 4)
         for name in layouts:
             res[f"{kind}_{name}_over_flat"] = round(med[f"{kind}_{name}"] / min(a, b), 3)
+            if args.bits4:
+                res[f"{kind}_{name}_over_int8"] = round(
+                    med[f"{kind}_{name}"] / med[f"{kind}8_{name}"], 3)
     print(json.dumps(res), flush=True)
 
 
@@ -145,9 +173,10 @@ def bucket(args):
              for _ in range(nt)]
     d = mx.Distribution(size, 1)
     flat_req = mx.PersistentRequest(d, "all_reduce", per * nt, dtype=args.dtype, op="sum",
-                                    group="data", quantized=True)
+                                    group="data", quantized=True, bits=4 if args.bits4 else 8)
     seg_req = mx.SegmentedAllReduce(d, [per] * nt, dtype=args.dtype, group="data",
-                                    post_scale=1.0 / size)
+                                    post_scale=1.0 / size,
+                                    compression="int4" if args.bits4 else "int8")
 
     def flat():
         buf = torch.cat([g.reshape(-1) for g in grads])
@@ -186,7 +215,8 @@ def bucket(args):
         for k, fn in variants.items():
             times[k].append(timed(fn))
     if rank == 0:
-        res = {"config": "ddp-bucket", "dtype": args.dtype, "bucket_mib": per * nt * es >> 20,
+        res = {"config": "ddp-bucket", "bits": 4 if args.bits4 else 8, "dtype": args.dtype,
+               "bucket_mib": per * nt * es >> 20,
                "tensors": nt, "world": size, "iters": args.iters, "rounds": args.rounds,
                **{f"{k}_ms": _stats(v) for k, v in times.items()}}
         res["segments_over_flat"] = round(res["segments_ms"]["median"] /
@@ -205,6 +235,9 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--bits4", action="store_true", help="the int4 wire")
+    ap.add_argument("--path", default=None, choices=["fast", "generic"],
+                    help="with --bits4 in kernels mode: the int4 list kernels' path")
     args = ap.parse_args()
     {"kernels": kernels, "bucket": bucket}[args.mode](args)
 

@@ -568,20 +568,31 @@ class SegmentedAllReduce:
     counts: elements per tensor, each >= 1; dtype "f32" or "bf16".
     ar_algo: None takes MLSL_QUANT_AR_ALGO (ring unless set); "ring" or
     "two_shot" names it (two_shot: at most 8 ranks).
+    compression: "int8", or "int4" for the 4-bit wire (block / 2 + 8 bytes a
+    block where int8 takes block + 8): bit for bit the flat ``bits=4`` request
+    times ``float32(post_scale)``. It runs two_shot only: ar_algo=None means
+    two_shot whatever MLSL_QUANT_AR_ALGO says, "ring" is refused, as are more
+    than 8 ranks and a block that is no multiple of 8.
     Refused at creation: any other dtype, an empty list, a zero count, a
-    compression plugin. One bucket of DistributedData(compression="int8") is
-    one such request."""
+    compression plugin. One bucket of DistributedData(compression="int8" or
+    "int4") is one such request."""
 
     def __init__(self, dist, counts, dtype="f32", group="global", ar_algo=None,
-                 post_scale=1.0):
+                 post_scale=1.0, compression="int8"):
         if ar_algo is not None and ar_algo not in QUANT_AR_ALGO:
             raise ValueError(f"ar_algo={ar_algo!r}: expected None, 'ring' or 'two_shot'")
+        if compression not in ("int8", "int4"):
+            raise ValueError(f"compression={compression!r}: expected 'int8' or 'int4'")
         L = lib()
         if not hasattr(L, "_segments_declared"):
             P = ctypes.POINTER
             L.mlsl_persistent_all_reduce_quantized_segments.argtypes = [
                 c_void_p, P(c_size_t), c_size_t, c_int, c_int, c_int, ctypes.c_float,
                 P(c_void_p)]
+            L.mlsl_persistent_all_reduce_quantized_segments_bits.argtypes = [
+                c_void_p, P(c_size_t), c_size_t, c_int, c_int, c_int, ctypes.c_float, c_int,
+                P(c_void_p)]
+            L.mlsl_persistent_all_reduce_quantized_segments_bits.restype = c_int
             L.mlsl_request_start_segments.argtypes = [c_void_p, P(c_void_p), c_size_t]
             L.mlsl_request_wait.argtypes = [c_void_p, P(c_void_p)]
             L.mlsl_request_test.argtypes = [c_void_p, P(c_int)]
@@ -595,10 +606,16 @@ class SegmentedAllReduce:
         self._h = None
         self.nseg = len(counts)
         h = c_void_p()
-        check(L.mlsl_persistent_all_reduce_quantized_segments(
-            dist._h, _sizes(counts), len(counts), DTYPE[dtype], GROUP[group],
-            -1 if ar_algo is None else QUANT_AR_ALGO[ar_algo], post_scale,
-            ctypes.byref(h)))
+        algo = -1 if ar_algo is None else QUANT_AR_ALGO[ar_algo]
+        if compression == "int4":
+            # "ring" raises the library's message
+            check(L.mlsl_persistent_all_reduce_quantized_segments_bits(
+                dist._h, _sizes(counts), len(counts), DTYPE[dtype], GROUP[group], algo,
+                post_scale, 4, ctypes.byref(h)))
+        else:
+            check(L.mlsl_persistent_all_reduce_quantized_segments(
+                dist._h, _sizes(counts), len(counts), DTYPE[dtype], GROUP[group], algo,
+                post_scale, ctypes.byref(h)))
         self._h = h
         self._ptrs = (c_void_p * max(1, len(counts)))()
 

@@ -315,6 +315,77 @@ int mlsl_hip_dequantize_scatter_tables(const void* wire, void* const* dev_ptrs,
     OPS_CATCH
 }
 
+// The list codec on the int4 wire; path as in mlsl_hip_quantize4.
+int mlsl_hip_quantize_gather4(const void* const* ptrs, const size_t* counts, size_t nseg,
+                              void* err, void* wire, size_t block, int dt, int use_err,
+                              int path) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_hip_quantize_gather4", 4);
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "quantize-gather");
+    DevSegTables tab(offs, ptrs);
+    LaunchQuantizeGather4(tab.ptrs, tab.offs, nseg, err, wire, count, block,
+                          static_cast<DataType>(dt), use_err != 0, nullptr,
+                          static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_dequantize_scatter4(const void* wire, void* const* ptrs, const size_t* counts,
+                                 size_t nseg, size_t block, int dt, float post_scale,
+                                 int round_first, int path) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_hip_dequantize_scatter4", 4);
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "dequantize-scatter");
+    DevSegTables tab(offs, ptrs);
+    LaunchDequantizeScatter4(wire, tab.ptrs, tab.offs, nseg, count, block,
+                             static_cast<DataType>(dt), post_scale, round_first != 0, nullptr,
+                             static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_quantize_gather4_tables(const void* const* dev_ptrs, const uint64_t* dev_offs,
+                                     size_t nseg, void* err, void* wire, size_t count,
+                                     size_t block, int dt, int use_err, int path) {
+    OPS_TRY LaunchQuantizeGather4(dev_ptrs, dev_offs, nseg, err, wire, count, block,
+                                  static_cast<DataType>(dt), use_err != 0, nullptr,
+                                  static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_dequantize_scatter4_tables(const void* wire, void* const* dev_ptrs,
+                                        const uint64_t* dev_offs, size_t nseg, size_t count,
+                                        size_t block, int dt, float post_scale,
+                                        int round_first, int path) {
+    OPS_TRY LaunchDequantizeScatter4(wire, dev_ptrs, dev_offs, nseg, count, block,
+                                     static_cast<DataType>(dt), post_scale, round_first != 0,
+                                     nullptr, static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_host_quantize_gather4(const void* const* ptrs, const size_t* counts, size_t nseg,
+                               void* err, void* wire, size_t block, int dt, int use_err) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_quantize_gather4", 4);
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "quantize-gather");
+    HostQuantizeGather(ptrs, offs.data(), nseg, err, wire, count, block,
+                       static_cast<DataType>(dt), use_err != 0, 4);
+    OPS_CATCH
+}
+
+int mlsl_host_dequantize_scatter4(const void* wire, void* const* ptrs, const size_t* counts,
+                                  size_t nseg, size_t block, int dt, float post_scale,
+                                  int round_first) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_dequantize_scatter4", 4);
+    size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "dequantize-scatter");
+    HostDequantizeScatter(wire, ptrs, offs.data(), nseg, count, block,
+                          static_cast<DataType>(dt), post_scale, round_first != 0, 4);
+    OPS_CATCH
+}
+
 // quantize-gather of the list padded with zeros to nshards * shard elements,
 // shard by shard: wire j at wire + j * wire_stride, the residual flat.
 int mlsl_hip_quantize_gather_shards(const void* const* ptrs, const size_t* counts, size_t nseg,

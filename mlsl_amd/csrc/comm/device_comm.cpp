@@ -665,14 +665,19 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
                                        base + p.send_seg * p.seg_wire,
                                        static_cast<size_t>(req->SegOffs().back()), p.nseg,
                                        p.count, p.seg_wire, p.block, dt, p.residual, s);
+        else if (p.bits == 4)
+            LaunchQuantizeGather4(seg_ptrs, seg_offs, nseg,
+                                  p.residual ? base + p.err_off : nullptr,
+                                  base + p.send_seg * p.seg_wire, p.count, p.block, dt,
+                                  p.residual, s);
         else
             LaunchQuantizeGather(seg_ptrs, seg_offs, nseg,
                                  p.residual ? base + p.err_off : nullptr,
                                  base + p.send_seg * p.seg_wire, p.count, p.block, dt,
                                  p.residual, s);
     } else {
-        // p.bits == 4: the int4 codec (flat two-shot allreduce and direct
-        // reduce-scatter only; Setup() refused everything else)
+        // p.bits == 4: the int4 codec (two-shot allreduce, flat or over a list,
+        // and flat direct reduce-scatter only; Setup() refused everything else)
         for (size_t j = 0; j < p.nseg; ++j) {
             const uint8_t* in = sbuf + j * p.seg_bytes;
             uint8_t* err = p.residual ? base + p.err_off + j * p.seg_bytes : nullptr;
@@ -695,7 +700,10 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
             LaunchQuantSumDequant(wires[0], wires[1], rbuf, p.count, p.block, dt, s);
             break;
         case QuantFinish::DEQUANT:
-            if (seg && !seg_rs)
+            if (seg && !seg_rs && p.bits == 4)
+                LaunchDequantizeScatter4(wires[0], seg_ptrs, seg_offs, nseg, p.count, p.block,
+                                         dt, req->PostScale(), /*round_first=*/true, s);
+            else if (seg && !seg_rs)
                 // round_first: the flat request's bits, then scaled
                 LaunchDequantizeScatter(wires[0], seg_ptrs, seg_offs, nseg, p.count, p.block,
                                         dt, req->PostScale(), /*round_first=*/true, s);

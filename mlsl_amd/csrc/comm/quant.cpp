@@ -332,8 +332,8 @@ void CheckSegTables(const void* ptrs, const uint64_t* offs, size_t nseg, size_t 
 
 void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
                         void* err, void* wire, size_t count, size_t block, DataType dt,
-                        bool use_err) {
-    CheckQuantBlock(block, "HostQuantizeGather");
+                        bool use_err, int bits) {
+    CheckQuantBlock(block, "HostQuantizeGather", bits);
     CheckSegTables(seg_ptrs, seg_offs, nseg, count, dt, "quantize-gather");
     SegCursor cur{seg_offs, nseg};
     // HostQuantize's two instantiations, reading through the cursor
@@ -344,7 +344,7 @@ void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, s
             return static_cast<const float*>(seg_ptrs[cur.s])[k];
         };
         QuantizeImpl([&](size_t i, bool ue) { return ue ? in(i) + e[i] : in(i); },
-                     [&](size_t i, float v) { e[i] = v; }, wire, count, block, use_err);
+                     [&](size_t i, float v) { e[i] = v; }, wire, count, block, use_err, bits);
     } else {
         uint16_t* e = static_cast<uint16_t*>(err);
         auto in = [&](size_t i) {
@@ -352,7 +352,8 @@ void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, s
             return Bf16F(static_cast<const uint16_t*>(seg_ptrs[cur.s])[k]);
         };
         QuantizeImpl([&](size_t i, bool ue) { return ue ? in(i) + Bf16F(e[i]) : in(i); },
-                     [&](size_t i, float v) { e[i] = F32B(v); }, wire, count, block, use_err);
+                     [&](size_t i, float v) { e[i] = F32B(v); }, wire, count, block, use_err,
+                     bits);
     }
 }
 
@@ -409,8 +410,8 @@ void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_o
 
 void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64_t* seg_offs,
                            size_t nseg, size_t count, size_t block, DataType dt,
-                           float post_scale, bool round_first) {
-    CheckQuantBlock(block, "HostDequantizeScatter");
+                           float post_scale, bool round_first, int bits) {
+    CheckQuantBlock(block, "HostDequantizeScatter", bits);
     const bool pre_round = round_first && dt == DataType::BF16;
     CheckSegTables(seg_ptrs, seg_offs, nseg, count, dt, "dequantize-scatter");
     SegCursor cur{seg_offs, nseg};
@@ -419,15 +420,15 @@ void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64
     for (size_t b = 0; b < nblocks; ++b) {
         const size_t base = b * block;
         const size_t n = std::min(block, count - base);
-        const uint8_t* wb = w + b * (block + kWireHdr);
+        const uint8_t* wb = w + b * WireBlock(block, bits);
         float scale;
         std::memcpy(&scale, wb, 4);
-        const int8_t* payload = reinterpret_cast<const int8_t*>(wb + kWireHdr);
+        const uint8_t* payload = wb + kWireHdr;
         for (size_t i = 0; i < n; ++i) {
             const size_t k = cur.Seek(base + i);
             // two roundings to float, as the device kernel: never one product
             // with scale * post_scale
-            float dq = payload[i] * scale;
+            float dq = PayloadGet(payload, i, bits) * scale;
             if (pre_round) dq = Bf16F(F32B(dq));
             const float v = dq * post_scale;
             if (dt == DataType::F32) static_cast<float*>(seg_ptrs[cur.s])[k] = v;

@@ -66,10 +66,11 @@ void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t cou
 // pointers aligned to the element size only.
 // Gather: wire, and the flat residual err of count elements when use_err, get
 // the bytes HostQuantize writes for V; the tensors are only read. Bit for bit
-// what LaunchQuantizeGather computes.
+// what LaunchQuantizeGather computes; at bits = 4 what LaunchQuantizeGather4
+// and LaunchDequantizeScatter4 do, the residual included.
 void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
                         void* err, void* wire, size_t count, size_t block, DataType dt,
-                        bool use_err);
+                        bool use_err, int bits = 8);
 // Prologue of the quantized reduce-scatter over a list of tensors: V' is V
 // (`total` elements, the tables above) followed by zeros up to nshards * shard
 // elements, and shard j of V' gets HostQuantize's bytes at wire + j *
@@ -92,7 +93,7 @@ void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_o
 // the request's finish uses it.
 void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64_t* seg_offs,
                            size_t nseg, size_t count, size_t block, DataType dt,
-                           float post_scale, bool round_first = false);
+                           float post_scale, bool round_first = false, int bits = 8);
 
 // dlopen'd compression plugin (reference quant/quant.c ABI — Intel
 // DL-comp style). Loaded once per lib_path; used by the HOST compressed

@@ -279,9 +279,9 @@ void CommRequest::BuildChunks() {
                        "plugin declares its own wire block); unset lib_path or use bits=8");
             MLSL_CHECK(spec_.op != CollOp::ALLGATHER && spec_.op != CollOp::ALLGATHERV,
                        "the 4-bit wire codec is not wired to all_gather; use bits=8");
-            MLSL_CHECK(!Segmented(),
-                       "the 4-bit wire codec is not wired to requests over a tensor list; "
-                       "use bits=8");
+            MLSL_CHECK(!SegmentedReduceScatter(),
+                       "the 4-bit wire codec is not wired to the reduce_scatter over a tensor "
+                       "list (the all_reduce over a tensor list is); use bits=8");
             MLSL_CHECK(Compressed(),
                        "the 4-bit wire codec serves all_reduce and reduce_scatter sums of "
                        "f32/bf16 only");
@@ -814,7 +814,7 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                 HostQuantizeGather(seg_ptrs_.data(), seg_offs_.data(), seg_ptrs_.size(),
                                    qp.residual ? wire + qp.err_off : nullptr,
                                    wire + qp.send_seg * qp.seg_wire, qp.count, qp.block,
-                                   dtype_, qp.residual);
+                                   dtype_, qp.residual, qp.bits);
             const size_t flat_segs = Segmented() ? 0 : qp.nseg;
             for (size_t j = 0; j < flat_segs; ++j) {
                 const uint8_t* seg = sbase + j * qp.seg_bytes;
@@ -943,7 +943,7 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                                                           seg_offs_.data(), seg_ptrs_.size(),
                                                           qp.count, qp.block, dtype_,
                                                           post_scale_,
-                                                          /*round_first=*/true);
+                                                          /*round_first=*/true, qp.bits);
                                 else
                                     HostDequantize(wires[0], rbase, qp.count, qp.block, dtype_,
                                                    qp.bits);

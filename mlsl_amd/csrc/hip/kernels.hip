@@ -2424,6 +2424,324 @@ void LaunchDequantizeScatter(const void* wire, void* const* seg_ptrs,
     HIP_CHECK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------
+// The same two list kernels on the int4 wire: the prologue and the finish of
+// the allreduce over a list at 4 bits. A payload byte holds two elements and a
+// payload word eight, so with boundaries anywhere one word can hold elements of
+// up to eight tensors. Ownership settles that: a lane owns whole payload
+// words, eight consecutive elements of V and one 4-byte wire access, and no
+// two lanes ever touch one payload byte.
+//
+// Split of work, X2: block 256 takes one block per 32-lane half-wave, lane
+// `sub` owning word `sub` (two blocks per wave, the int4 flat kernels' fast
+// layout); otherwise one wave per block, lanes owning words lane, lane + 64,
+// ... Both handle a partial last block. The wave finds the tensor of its
+// (lower) block's first element once, uniform, by SegCursor's bisection; each
+// lane then decides for its own word: eight elements inside one tensor at a
+// 16-byte aligned address are one vector access (two for f32), anything else
+// walks the table forward element by element, guarded by the block's n. A
+// block crossed by one boundary so loses only the straddling word to the walk.
+// Where a lane owns one word per block (every block up to 512 elements) its
+// eight values, residual added, stay in registers across the maximum: every
+// tensor and residual byte is read once. The residual is flat and block-
+// aligned in V, so its accesses are vector wherever err + base + 8w is 16-byte
+// aligned, whatever the tensors' alignment is.
+//
+// Like the int4 section above, and for its reason, these kernels are compiled
+// without packed fp32 instructions: they are pinned bit for bit to the flat
+// int4 kernels and to the host twins.
+
+namespace {
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+
+__device__ __forceinline__ bool Aligned16(const void* p) {
+    return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+}
+
+// A lane's own position in the table: it starts at the wave's tensor and only
+// ever moves forward, as the lane's elements ascend.
+template <typename T>
+struct LaneSeg {
+    uint32_t s;
+    uint64_t lo, hi;   // tensor s holds V[lo, hi)
+    T* p;
+    __device__ __forceinline__ explicit LaneSeg(const SegCursor<T>& c)
+        : s(c.seg), lo(c.lo), hi(c.hi), p(c.ptr) {}
+    // the address of V[e], e at or past the last element asked for
+    template <typename P>
+    __device__ __forceinline__ T* At(const SegTable& t, P ptrs, uint64_t e) {
+        if (e >= hi) {
+            // the table's last entry bounds the walk whatever `count` says
+            while (e >= hi && s + 1 < t.nseg) hi = t.offs[++s + 1];
+            lo = t.offs[s];
+            p = ptrs[s];
+        }
+        return p + (e - lo);
+    }
+};
+
+// The nv (0 to 8) values of the word that starts at V[e0], residual added,
+// into v; the rest of v is 0. eb is the word's residual (USE_ERR only).
+template <typename T, bool USE_ERR, typename P>
+__device__ __forceinline__ void GatherWord4(const SegTable& t, P ptrs, LaneSeg<const T>& ls,
+                                            uint64_t e0, int nv, const T* eb, float v[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    if (nv <= 0) return;
+    const T* p = ls.At(t, ptrs, e0);
+    if (nv == 8 && e0 + 8 <= ls.hi && Aligned16(p)) {
+        Load8(p, v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < nv) v[j] = Decode(*ls.At(t, ptrs, e0 + j));
+    }
+    if constexpr (USE_ERR) {
+        if (nv == 8 && Aligned16(eb)) {
+            float e[8];
+            Load8(eb, e);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] += e[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < nv) v[j] += Decode(eb[j]);
+        }
+    }
+}
+
+// Quantizes the word in v, which is left holding the residuals; stores the nv
+// of them with USE_ERR. Returns the payload word: a value of 0 packs as 0.
+template <typename T, bool USE_ERR>
+__device__ __forceinline__ uint32_t QuantizeWord4(float v[8], float scale, float inv, int nv,
+                                                  T* eb) {
+    uint32_t packed = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float q = QRound<kQ4Max>(v[j], inv);
+        packed |= QPack4(q, j);
+        v[j] = QResidual(v[j], q, scale);
+    }
+    if constexpr (USE_ERR) {
+        if (nv == 8 && Aligned16(eb)) {
+            Store8<false>(eb, v);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (j < nv) eb[j] = Encode<T>(v[j]);
+        }
+    }
+    return packed;
+}
+
+template <typename T, bool USE_ERR, bool X2>
+__global__ void QuantizeGather4Kernel(const T* const* __restrict__ ptrs, SegTable tab,
+                                      T* __restrict__ err, uint8_t* __restrict__ wire,
+                                      size_t count, size_t block_arg) {
+    constexpr int TEAM = X2 ? 32 : 64;   // lanes per block
+    const size_t block_elems = X2 ? kFastBlock : block_arg;
+    const size_t words = block_elems / 8;
+    const size_t nblocks = (count + block_elems - 1) / block_elems;
+    SegCursor<const T> cur;
+    ForEachWaveBlock(X2 ? (nblocks + 1) / 2 : nblocks, [&](size_t vunit, int lane) {
+        // uniform across the wave: the bisection stays in scalar registers
+        const size_t first = WaveUniform(vunit) * (X2 ? 2 : 1);
+        cur.Seek(tab, ptrs, first * block_elems);
+        const size_t blk = X2 ? first + (lane >> 5) : first;
+        const size_t sub = X2 ? (lane & 31) : lane;
+        if (blk >= nblocks) return;   // the idle half of the last pair
+        const size_t base = blk * block_elems;
+        const size_t n = min(block_elems, count - base);
+        uint8_t* wblock = wire + blk * Wire4BlockBytes(block_elems);
+        uint32_t* payload = reinterpret_cast<uint32_t*>(wblock + kWireHdr);
+        auto valid = [&](size_t w) {
+            return w * 8 >= n ? 0 : static_cast<int>(min(size_t(8), n - w * 8));
+        };
+        auto eb = [&](size_t w) { return USE_ERR ? err + base + w * 8 : nullptr; };
+        auto team_max = [&](float m) { return X2 ? HalfWaveMax(m) : WaveMax(m); };
+        LaneSeg<const T> ls(cur);
+        float v[8];
+        if (words <= TEAM) {
+            // one word per lane: read once, kept across the maximum
+            const int nv = sub < words ? valid(sub) : 0;
+            GatherWord4<T, USE_ERR>(tab, ptrs, ls, base + sub * 8, nv, eb(sub), v);
+            float m = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[j]));
+            const float scale = QScale<kQ4Max>(team_max(m));
+            if (sub == 0) WriteWireHeader(wblock, scale);
+            if (sub < words)
+                payload[sub] = QuantizeWord4<T, USE_ERR>(v, scale, 1.f / scale, nv, eb(sub));
+        } else {
+            float m = 0.f;
+            for (size_t w = sub; w * 8 < n; w += TEAM) {
+                GatherWord4<T, USE_ERR>(tab, ptrs, ls, base + w * 8, valid(w), eb(w), v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[j]));
+            }
+            const float scale = QScale<kQ4Max>(team_max(m));
+            if (sub == 0) WriteWireHeader(wblock, scale);
+            const float inv = 1.f / scale;
+            ls = LaneSeg<const T>(cur);
+            for (size_t w = sub; w < words; w += TEAM) {
+                const int nv = valid(w);
+                GatherWord4<T, USE_ERR>(tab, ptrs, ls, base + w * 8, nv, eb(w), v);
+                payload[w] = QuantizeWord4<T, USE_ERR>(v, scale, inv, nv, eb(w));
+            }
+        }
+    });
+}
+
+// The nv (1 to G) first of the G = 16 / sizeof(T) elements V[e0, e0 + G) from
+// the low G nibbles of `bits`: one 16-byte store when all G lie inside one
+// tensor at an aligned address, else element by element through the table.
+// Two roundings to float, then one into T: never (scale * post_scale).
+template <typename T, bool ROUND_FIRST, typename P>
+__device__ __forceinline__ void ScatterGroup4(const SegTable& t, P ptrs, LaneSeg<T>& ls,
+                                              uint64_t e0, int nv, uint32_t bits, float scale,
+                                              float post_scale) {
+    constexpr int G = 16 / sizeof(T);
+    using V = std::conditional_t<sizeof(T) == 4, float4_ev, ushort8_t>;
+    if (nv <= 0) return;
+    V o;
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        float dq = QUnpack4(bits, j) * scale;
+        if constexpr (ROUND_FIRST) dq = Decode<T>(Encode<T>(dq));
+        o[j] = Encode<T>(dq * post_scale);
+    }
+    T* p = ls.At(t, ptrs, e0);
+    if (nv == G && e0 + G <= ls.hi && Aligned16(p)) {
+        StoreVec<false>(o, p);
+    } else {
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+            if (j < nv) *ls.At(t, ptrs, e0 + j) = o[j];
+    }
+}
+
+// Plain stores: the optimizer reads the gradients next. bf16, and every block
+// but 256: the lane's own words, eight elements each (f32: two groups of
+// four, each decided on its own). f32 at X2 takes Dequantize4X2Kernel's
+// split-half layout instead, for its reason: lane `sub` stores elements
+// [4 sub, +4) and [128 + 4 sub, +4) from the low or high half of words
+// sub >> 1 and 16 + (sub >> 1), so that each store is contiguous across the
+// half-wave where the tensors allow vector stores at all.
+template <typename T, bool ROUND_FIRST, bool X2>
+__global__ void DequantizeScatter4Kernel(const uint8_t* __restrict__ wire, T* const* ptrs,
+                                         SegTable tab, size_t count, size_t block_arg,
+                                         float post_scale) {
+    constexpr int TEAM = X2 ? 32 : 64;
+    constexpr int G = 16 / sizeof(T);
+    const size_t block_elems = X2 ? kFastBlock : block_arg;
+    const size_t nblocks = (count + block_elems - 1) / block_elems;
+    SegCursor<T> cur;
+    ForEachWaveBlock(X2 ? (nblocks + 1) / 2 : nblocks, [&](size_t vunit, int lane) {
+        const size_t first = WaveUniform(vunit) * (X2 ? 2 : 1);
+        cur.Seek(tab, ptrs, first * block_elems);
+        const size_t blk = X2 ? first + (lane >> 5) : first;
+        const size_t sub = X2 ? (lane & 31) : lane;
+        if (blk >= nblocks) return;
+        const size_t base = blk * block_elems;
+        const size_t n = min(block_elems, count - base);
+        const uint8_t* wblock = wire + blk * Wire4BlockBytes(block_elems);
+        const float scale = WireScale(wblock);
+        const uint32_t* payload = reinterpret_cast<const uint32_t*>(wblock + kWireHdr);
+        LaneSeg<T> ls(cur);
+        // the group of G elements at `off` in the block, from `bits`
+        auto group = [&](size_t off, uint32_t bits) {
+            const int nv = off >= n ? 0 : static_cast<int>(min(size_t(G), n - off));
+            ScatterGroup4<T, ROUND_FIRST>(tab, ptrs, ls, base + off, nv, bits, scale,
+                                          post_scale);
+        };
+        if constexpr (X2 && sizeof(T) == 4) {
+            const int shift = (sub & 1) * 16;
+            if (sub * 4 < n) group(sub * 4, payload[sub >> 1] >> shift);
+            if (128 + sub * 4 < n) group(128 + sub * 4, payload[16 + (sub >> 1)] >> shift);
+        } else {
+            for (size_t w = sub; w * 8 < n; w += TEAM) {
+                const uint32_t packed = payload[w];
+#pragma unroll
+                for (int g = 0; g < 8 / G; ++g) group(w * 8 + g * G, packed >> (4 * G * g));
+            }
+        }
+    });
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
+// AUTO takes the half-wave layout wherever it applies: at block 256.
+bool TakeSegFast4(Quant4Path path, size_t block_elems, const char* who) {
+    MLSL_CHECK(path != Quant4Path::FAST || block_elems == kFastBlock,
+               std::string(who) + ": the fast path needs block 256");
+    return path != Quant4Path::GENERIC && block_elems == kFastBlock;
+}
+
+}  // namespace
+
+void LaunchQuantizeGather4(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                           void* err, void* wire, size_t count, size_t block_elems,
+                           DataType dt, bool use_err, hipStream_t stream, Quant4Path path) {
+    CheckQuantBlock(block_elems, "LaunchQuantizeGather4", 4);
+    CheckSegArgs(seg_ptrs, seg_offs, nseg, count, dt, "int4 quantize-gather");
+    MLSL_CHECK((reinterpret_cast<uintptr_t>(wire) & 3) == 0,
+               "int4 quantize-gather: the wire must be 4-byte aligned");
+    MLSL_CHECK(!use_err || err != nullptr, "int4 quantize-gather: use_err without err");
+    const bool fast = TakeSegFast4(path, block_elems, "LaunchQuantizeGather4");
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const size_t nblocks = NumBlocks(count, block_elems);
+    const dim3 grid = fast ? PairGrid(nblocks) : WaveGrid(nblocks);
+    uint8_t* w = static_cast<uint8_t*>(wire);
+    auto launch = [&](auto* e) {
+        using T = std::remove_pointer_t<decltype(e)>;
+        DispatchBool(use_err, [&](auto ue) {
+            DispatchBool(fast, [&](auto x2) {
+                QuantizeGather4Kernel<T, decltype(ue)::value, decltype(x2)::value>
+                    <<<grid, dim3(kBlock), 0, stream>>>(
+                        reinterpret_cast<const T* const*>(seg_ptrs), tab, e, w, count,
+                        block_elems);
+            });
+        });
+    };
+    if (dt == DataType::F32) launch(static_cast<float*>(err));
+    else launch(static_cast<unsigned short*>(err));
+    HIP_CHECK(hipGetLastError());
+}
+
+void LaunchDequantizeScatter4(const void* wire, void* const* seg_ptrs,
+                              const uint64_t* seg_offs, size_t nseg, size_t count,
+                              size_t block_elems, DataType dt, float post_scale,
+                              bool round_first, hipStream_t stream, Quant4Path path) {
+    CheckQuantBlock(block_elems, "LaunchDequantizeScatter4", 4);
+    CheckSegArgs(seg_ptrs, seg_offs, nseg, count, dt, "int4 dequantize-scatter");
+    MLSL_CHECK((reinterpret_cast<uintptr_t>(wire) & 3) == 0,
+               "int4 dequantize-scatter: the wire must be 4-byte aligned");
+    const bool fast = TakeSegFast4(path, block_elems, "LaunchDequantizeScatter4");
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const size_t nblocks = NumBlocks(count, block_elems);
+    const dim3 grid = fast ? PairGrid(nblocks) : WaveGrid(nblocks);
+    const uint8_t* w = static_cast<const uint8_t*>(wire);
+    auto launch = [&](auto* elem, auto rf) {
+        using T = std::remove_pointer_t<decltype(elem)>;
+        DispatchBool(fast, [&](auto x2) {
+            DequantizeScatter4Kernel<T, decltype(rf)::value, decltype(x2)::value>
+                <<<grid, dim3(kBlock), 0, stream>>>(w, reinterpret_cast<T* const*>(seg_ptrs),
+                                                    tab, count, block_elems, post_scale);
+        });
+    };
+    // q * scale already is an f32: rounding it first changes nothing
+    if (dt == DataType::F32) launch(static_cast<float*>(nullptr), std::false_type{});
+    else DispatchBool(round_first, [&](auto rf) {
+        launch(static_cast<unsigned short*>(nullptr), rf);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
 // --- IPC p2p transport (comm/p2p_transport.cpp) ---
 // Mailboxes are monotonically increasing u64 sequence counters in the
 // receiver's HBM window; the writer is a remote process on the same or a

@@ -176,6 +176,27 @@ void LaunchDequantizeScatter(const void* wire, void* const* seg_ptrs,
                              const uint64_t* seg_offs, size_t nseg, size_t count,
                              size_t block_elems, DataType dt, float post_scale,
                              bool round_first, hipStream_t stream);
+// The same pair on the int4 wire, same tables. Gather: `wire`, and `err` when
+// use_err, get the bytes LaunchQuantize4 writes for V (the residual is its
+// one explicit fma, so pinned exactly; nibbles past `count` and the header's
+// second word are 0). Scatter: Encode((q * scale) * post_scale) as above, with
+// post_scale == 1.0f the bits of LaunchDequantize4; plain stores. block_elems
+// is a non-zero multiple of 8 and the wire 4-byte aligned. A lane owns whole
+// payload words (eight elements), so a byte whose nibbles come from two
+// tensors needs no special case. FAST is one block per half-wave and needs
+// block 256 (it throws elsewhere), GENERIC one wave per block; AUTO takes FAST
+// at block 256. Both take partial last blocks and any tensor alignment. The
+// grids are the flat int4 kernels': Quant4BlocksPerTrip holds. The host twins
+// (comm/quant.hpp, bits = 4) compute the same bits.
+void LaunchQuantizeGather4(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                           void* err, void* wire, size_t count, size_t block_elems,
+                           DataType dt, bool use_err, hipStream_t stream,
+                           Quant4Path path = Quant4Path::AUTO);
+void LaunchDequantizeScatter4(const void* wire, void* const* seg_ptrs,
+                              const uint64_t* seg_offs, size_t nseg, size_t count,
+                              size_t block_elems, DataType dt, float post_scale,
+                              bool round_first, hipStream_t stream,
+                              Quant4Path path = Quant4Path::AUTO);
 
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,

@@ -132,7 +132,8 @@ int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
  * which at 4 bits loses far more than at 8. Also failing at creation at 4
  * bits: a group of more than 8 ranks, a compression plugin, a block that is
  * no multiple of 8; and any bits other than 4 or 8. The all-gather and the
- * requests over a tensor list have no 4-bit form. */
+ * reduce-scatter over a tensor list have no 4-bit form; the allreduce over a
+ * tensor list has one (mlsl_persistent_all_reduce_quantized_segments_bits). */
 int mlsl_persistent_all_reduce_quantized_bits(mlsl_distribution d, size_t count,
                                               mlsl_data_type dt, mlsl_reduction op,
                                               mlsl_group g, int algo, int bits,
@@ -164,6 +165,18 @@ int mlsl_persistent_all_reduce_quantized_segments(mlsl_distribution d, const siz
                                                   size_t nseg, mlsl_data_type dt,
                                                   mlsl_group g, int algo, float post_scale,
                                                   mlsl_request* out);
+/* The same request with the payload bits of its wire named: bits == 8 is the
+ * function above. bits == 4 is the int4 wire of
+ * mlsl_persistent_all_reduce_quantized_bits, with that function's rules: it
+ * runs two-shot only (algo -1 or 1, MLSL_QUANT_AR_ALGO is not read; 0, the
+ * ring, fails at creation), on at most 8 ranks, without a plugin, with a block
+ * that is a multiple of 8. Bit for bit the flat bits == 4 request's result
+ * times post_scale in float; the residual is pinned exactly (one fma). */
+int mlsl_persistent_all_reduce_quantized_segments_bits(mlsl_distribution d,
+                                                       const size_t* counts, size_t nseg,
+                                                       mlsl_data_type dt, mlsl_group g,
+                                                       int algo, float post_scale, int bits,
+                                                       mlsl_request* out);
 int mlsl_request_start_segments(mlsl_request req, void* const* ptrs, size_t nseg);
 int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
                                    mlsl_data_type dt, mlsl_reduction op, mlsl_group g,

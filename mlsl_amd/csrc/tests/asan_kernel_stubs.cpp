@@ -105,6 +105,8 @@ void LaunchDequantizeSegments(const void* w, size_t nseg, void* out, size_t n, s
 void LaunchQuantizeGather(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGather, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st)
 void LaunchQuantizeGatherShards(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t total, size_t nshards, size_t shard, size_t stride, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGatherShards, ptrs, offs, nseg, err, w, total, nshards, shard, stride, blk, dt, use_err, st)
 void LaunchDequantizeScatter(const void* w, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, size_t blk, DataType dt, float post, bool round_first, hipStream_t st) STUB(LaunchDequantizeScatter, w, ptrs, offs, nseg, n, blk, dt, post, round_first, st)
+void LaunchQuantizeGather4(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st, Quant4Path path) STUB(LaunchQuantizeGather4, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st, path)
+void LaunchDequantizeScatter4(const void* w, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, size_t blk, DataType dt, float post, bool round_first, hipStream_t st, Quant4Path path) STUB(LaunchDequantizeScatter4, w, ptrs, offs, nseg, n, blk, dt, post, round_first, st, path)
 void LaunchPack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchPack, s, d, pd, dt, st)
 void LaunchUnpack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchUnpack, s, d, pd, dt, st)
 void LaunchWaitFlag(const void* mbox, uint64_t target, const void* abort_word, void* status, uint64_t max_ticks, hipStream_t st) STUB(LaunchWaitFlag, mbox, target, abort_word, status, max_ticks, st)

@@ -84,6 +84,19 @@ def _lib():
         L.mlsl_hip_dequantize_scatter_tables.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p,
                                                          c.c_size_t, c.c_size_t, c.c_size_t,
                                                          c.c_int, c.c_float, c.c_int]
+        L.mlsl_hip_quantize_gather4.argtypes = L.mlsl_hip_quantize_gather.argtypes + [c.c_int]
+        L.mlsl_hip_dequantize_scatter4.argtypes = \
+            L.mlsl_hip_dequantize_scatter.argtypes + [c.c_int]
+        L.mlsl_hip_quantize_gather4_tables.argtypes = \
+            L.mlsl_hip_quantize_gather_tables.argtypes + [c.c_int]
+        L.mlsl_hip_dequantize_scatter4_tables.argtypes = \
+            L.mlsl_hip_dequantize_scatter_tables.argtypes + [c.c_int]
+        L.mlsl_host_quantize_gather4.argtypes = L.mlsl_hip_quantize_gather.argtypes
+        L.mlsl_host_dequantize_scatter4.argtypes = L.mlsl_hip_dequantize_scatter.argtypes
+        for n in ("mlsl_hip_quantize_gather4", "mlsl_hip_dequantize_scatter4",
+                  "mlsl_hip_quantize_gather4_tables", "mlsl_hip_dequantize_scatter4_tables",
+                  "mlsl_host_quantize_gather4", "mlsl_host_dequantize_scatter4"):
+            getattr(L, n).restype = c.c_int
         L.mlsl_hip_quantize_gather_tables.restype = c.c_int
         L.mlsl_hip_dequantize_scatter_tables.restype = c.c_int
         L.mlsl_hip_quantize_gather_shards.argtypes = [c.POINTER(c.c_void_p),
@@ -379,6 +392,62 @@ def dequantize_scatter(wire, tensors, counts, block=256, dtype=None, post_scale=
                                              post_scale, 1 if round_first else 0))
 
 
+def quantize_gather4(tensors, counts, wire, err=None, block=256, dtype=None, path=None):
+    """`quantize_gather` into the int4 wire: exactly the bytes `quantize4`
+    writes for torch.cat(tensors), in `wire` and, if given, in the flat
+    residual `err` (one fma(-q, scale, v), pinned bit for bit). block is a
+    multiple of 8 and the wire 4-byte aligned. path=None takes one block per
+    half-wave at block 256 and one wave per block otherwise; "generic" or
+    "fast" names it ("fast" needs block 256)."""
+    _check_block4(block)
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather4(ptrs, cnts, nseg, ep, wp, block, DTYPE[dt],
+                                           1 if err is not None else 0, _PATH4[path]))
+
+
+def dequantize_scatter4(wire, tensors, counts, block=256, dtype=None, post_scale=1.0,
+                        round_first=False, path=None):
+    """`dequantize_scatter` of an int4 wire: (q * scale) * post_scale with
+    both products rounded to float32; post_scale=1.0 gives `dequantize4`'s
+    bits. round_first and path as in `dequantize_scatter` and
+    `quantize_gather4`."""
+    _check_block4(block)
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    wp, _ = _as_ptr_dtype(wire)
+    check(_lib().mlsl_hip_dequantize_scatter4(wp, ptrs, cnts, nseg, block, DTYPE[dt],
+                                              post_scale, 1 if round_first else 0,
+                                              _PATH4[path]))
+
+
+def quantize_gather4_tables(dev_ptrs, dev_offs, nseg, count, wire, err=None, block=256,
+                            dtype="f32", path=None):
+    """`quantize_gather4` over tables in DEVICE memory; see
+    `quantize_gather_tables`."""
+    _check_block4(block)
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    fp, _ = _as_ptr_dtype(dev_offs)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather4_tables(pp, fp, nseg, ep, wp, count, block,
+                                                  DTYPE[dtype], 1 if err is not None else 0,
+                                                  _PATH4[path]))
+
+
+def dequantize_scatter4_tables(wire, dev_ptrs, dev_offs, nseg, count, block=256, dtype="f32",
+                               post_scale=1.0, round_first=False, path=None):
+    """`dequantize_scatter4` over tables in DEVICE memory; see
+    `quantize_gather_tables`."""
+    _check_block4(block)
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    fp, _ = _as_ptr_dtype(dev_offs)
+    wp, _ = _as_ptr_dtype(wire)
+    check(_lib().mlsl_hip_dequantize_scatter4_tables(wp, pp, fp, nseg, count, block,
+                                                     DTYPE[dtype], post_scale,
+                                                     1 if round_first else 0, _PATH4[path]))
+
+
 def _shard_args(total, nshards, shard, wire_stride, block):
     """(nshards, shard, wire_stride) checked; wire_stride=None is one shard's
     wire bytes rounded up to 16."""
@@ -513,6 +582,26 @@ def host_dequantize_scatter(wire, arrays, counts, block=256, dtype="f32", post_s
     wp = _host_buf(wire, wire_bytes(total, block), "wire")
     check(_lib().mlsl_host_dequantize_scatter(wp, ptrs, cnts, nseg, block, DTYPE[dtype],
                                               post_scale, 1 if round_first else 0))
+
+
+def host_quantize_gather4(arrays, counts, wire, err=None, block=256, dtype="f32"):
+    """Host twin of `quantize_gather4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays")
+    wp = _host_buf(wire, wire_bytes(total, block, 4), "wire")
+    ep = None if err is None else _host_buf(err, total * _ELEM_BYTES[dtype], "err")
+    check(_lib().mlsl_host_quantize_gather4(ptrs, cnts, nseg, ep, wp, block, DTYPE[dtype],
+                                            1 if err is not None else 0))
+
+
+def host_dequantize_scatter4(wire, arrays, counts, block=256, dtype="f32", post_scale=1.0,
+                             round_first=False):
+    """Host twin of `dequantize_scatter4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays")
+    wp = _host_buf(wire, wire_bytes(total, block, 4), "wire")
+    check(_lib().mlsl_host_dequantize_scatter4(wp, ptrs, cnts, nseg, block, DTYPE[dtype],
+                                               post_scale, 1 if round_first else 0))
 
 
 def _host_buf(arr, need_bytes, what):

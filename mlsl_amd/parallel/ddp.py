@@ -24,6 +24,11 @@ finish_gradients() only waits. The average is (q * scale) * (1/world), two
 float32 roundings: the bits of a flat quantized allreduce of the bucket
 multiplied by float32(1/world). Buckets of any other dtype keep the exact path. Call
 close() to release the requests.
+
+compression="int4" is the same on the 4-bit wire (block / 2 + 8 bytes a block
+where int8 takes block + 8): the bits of a flat bits=4 request per bucket times
+float32(1/world). It runs the two-shot all_reduce only, so ar_algo is None or
+"two_shot" and the group has at most 8 ranks.
 """
 import torch
 
@@ -33,11 +38,16 @@ import mlsl_amd as mx
 class DistributedData:
     def __init__(self, module, dist=None, bucket_mb=25, group="data",
                  average=True, compression=None, ar_algo=None):
-        if compression not in (None, "int8"):
-            raise ValueError(f"compression={compression!r}: expected None or 'int8'")
+        if compression not in (None, "int8", "int4"):
+            raise ValueError(f"compression={compression!r}: expected None, 'int8' or 'int4'")
         if ar_algo is not None and compression is None:
             raise ValueError("ar_algo= selects the quantized all_reduce's algorithm: "
-                             "it needs compression='int8'")
+                             "it needs compression='int8' or 'int4'")
+        if compression == "int4" and ar_algo == "ring":
+            raise ValueError("compression='int4' does not run ar_algo='ring': the ring "
+                             "requantizes the partial sum on every hop, which at 4 bits "
+                             "loses far more than at 8; name 'two_shot' or nothing")
+        self.compression = compression
         self.module = module
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
         self.group = group
@@ -84,15 +94,15 @@ class DistributedData:
         self._pending = [0] * len(self._buckets)
         self._reqs = [None] * len(self._buckets)
         self._flat = [None] * len(self._buckets)
-        # compression="int8": one request over the bucket's gradient list per
-        # f32/bf16 bucket; None marks a bucket on the exact path
+        # compressed: one request over the bucket's gradient list per f32/bf16
+        # bucket; None marks a bucket on the exact path
         self._seg = [None] * len(self._buckets)
-        if compression == "int8" and self.world > 1:
+        if compression is not None and self.world > 1:
             for bi, ps in enumerate(self._buckets):
                 if ps[0].dtype in (torch.float32, torch.bfloat16):
                     self._seg[bi] = mx.SegmentedAllReduce(
                         self.dist, [q.numel() for q in ps], dtype=_dt(ps[0]),
-                        group=group, ar_algo=ar_algo,
+                        group=group, ar_algo=ar_algo, compression=compression,
                         post_scale=1.0 / self.world if average else 1.0)
 
         for p in self._params:
@@ -115,8 +125,8 @@ class DistributedData:
                 for q, g in zip(ps, grads):
                     if not g.is_contiguous():
                         raise ValueError(
-                            "compression='int8' reduces gradients in place and needs "
-                            f"them contiguous: the gradient of a parameter of shape "
+                            f"compression={self.compression!r} reduces gradients in place "
+                            f"and needs them contiguous: the gradient of a parameter of shape "
                             f"{tuple(q.shape)} has strides {g.stride()}")
                 self._seg[bi].start(grads)
                 self._reqs[bi] = self._seg[bi]
