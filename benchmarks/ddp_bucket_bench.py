@@ -25,6 +25,16 @@ tensors, against the int8 list kernels (gather8_*, scatter8_*); --path names
 the int4 list kernels' path (fast: one block per half-wave; generic: one wave
 per block). In bucket mode both requests run at 4 bits.
 
+--exact measures the exact list request instead. kernels: gather_list and
+scatter_scale_list (post_scale 1 and 1/3) against ops.copy of the same bytes
+(copy_a, copy_b), on 64 equal tensors at 16-byte aligned bases, on the same 64
+each one element past such a base, and on 4096 ragged tensors each at a
+16-byte aligned base of its own, as an allocator places them (so the tensor
+and flat addresses disagree modulo 16 after the first odd length). bucket: one
+SegmentedAllReduce(compression=None) against torch.cat, the flat exact
+request, a divide and one copy_ per tensor, on --tensors tensors (64 equal, or
+ragged).
+
 One JSON line per configuration. No GPU: exits with an error."""
 import argparse
 import json
@@ -156,6 +166,86 @@ def kernels(args):
     print(json.dumps(res), flush=True)
 
 
+def kernels_exact(args):
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("kernels mode measures GPU kernels: no GPU found")
+    from mlsl_amd import ops
+    torch.cuda.set_device(0)
+    es = 2 if args.dtype == "bf16" else 4
+    tdt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    total = (args.mbytes << 20) // es // 4096 * 4096
+    torch.manual_seed(0)
+    src = (torch.randn(total, dtype=torch.float32, device="cuda") * 0.01).to(tdt)
+    flat, back = torch.empty_like(src), torch.empty_like(src)
+    g = 16 // es   # elements per 16 bytes
+
+    def place(counts, shift):
+        """Tensors of `counts` elements in one arena, every base `shift`
+        elements past a 16-byte boundary, holding `src` in order."""
+        starts, pos = [], 0
+        for n in counts:
+            starts.append(pos + shift)
+            pos = (pos + shift + n + g - 1) // g * g
+        arena = torch.zeros(pos + g, dtype=tdt, device="cuda")
+        offs = [0]
+        for s, n in zip(starts, counts):
+            arena[s:s + n] = src[offs[-1]:offs[-1] + n]
+            offs.append(offs[-1] + n)
+        ptrs = [arena.data_ptr() + s * es for s in starts]
+        return (arena, torch.tensor(ptrs, dtype=torch.int64, device="cuda"),
+                torch.tensor(offs, dtype=torch.int64, device="cuda"), len(counts), starts)
+
+    layouts = {"aligned64": place([total // 64] * 64, 0), "off1_64": place([total // 64] * 64, 1),
+               "ragged4096": place(_ragged(total, 4096), 0)}
+    variants = {f"copy_{t}": (lambda: ops.copy(flat, src, total * es)) for t in ("a", "b")}
+    for name, (arena, pp, oo, n, starts) in layouts.items():
+        variants[f"gather_{name}"] = lambda pp=pp, oo=oo, n=n: ops.gather_list_tables(
+            pp, oo, n, total, flat, dtype=args.dtype)
+        for tag, ps in (("scatter1", 1.0), ("scatter3", 1.0 / 3.0)):
+            variants[f"{tag}_{name}"] = lambda pp=pp, oo=oo, n=n, ps=ps: \
+                ops.scatter_scale_list_tables(flat, pp, oo, n, total, dtype=args.dtype,
+                                              post_scale=ps)
+        # same bits before anything is timed: there and back again
+        flat.zero_()
+        ops.gather_list_tables(pp, oo, n, total, flat, dtype=args.dtype)
+        assert torch.equal(flat.view(torch.uint8), src.view(torch.uint8)), name
+        arena.zero_()
+        ops.scatter_scale_list_tables(flat, pp, oo, n, total, dtype=args.dtype)
+        ops.gather_list_tables(pp, oo, n, total, back, dtype=args.dtype)
+        assert torch.equal(back.view(torch.uint8), src.view(torch.uint8)), name
+
+    def timed(fn):
+        us = 0.0
+        for _ in range(args.iters):
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            us += e0.elapsed_time(e1) * 1e3
+        return us / args.iters
+
+    for fn in variants.values():
+        for _ in range(args.warmup):
+            fn()
+    times = {k: [] for k in variants}
+    for _ in range(args.rounds):
+        for k, fn in variants.items():
+            times[k].append(timed(fn))
+    med = {k: _stats(v)["median"] for k, v in times.items()}
+    a, b = med["copy_a"], med["copy_b"]
+    res = {"config": "list-exact-kernels", "dtype": args.dtype, "total_mib": total * es >> 20,
+           "iters": args.iters, "rounds": args.rounds,
+           **{f"{k}_us": _stats(v) for k, v in times.items()},
+           "copy_spread": round(abs(a - b) / min(a, b), 4)}
+    for k in variants:
+        if not k.startswith("copy_"):
+            res[f"{k}_over_copy"] = round(med[k] / min(a, b), 3)
+    print(json.dumps(res), flush=True)
+
+
 def bucket(args):
     import torch
     if not torch.cuda.is_available():
@@ -166,17 +256,26 @@ def bucket(args):
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)) % torch.cuda.device_count())
     es = 2 if args.dtype == "bf16" else 4
     tdt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    nt = 64
+    nt = args.tensors
     per = (args.mbytes << 20) // es // nt
+    # 64 equal tensors, or (--tensors other than 64) ragged ones of the same total
+    counts = [per] * nt if nt == 64 else _ragged(per * nt, nt)
     torch.manual_seed(1 + rank)
-    grads = [(torch.randn(per, dtype=torch.float32, device="cuda") * 0.01).to(tdt)
-             for _ in range(nt)]
+    grads = [(torch.randn(n, dtype=torch.float32, device="cuda") * 0.01).to(tdt)
+             for n in counts]
     d = mx.Distribution(size, 1)
-    flat_req = mx.PersistentRequest(d, "all_reduce", per * nt, dtype=args.dtype, op="sum",
-                                    group="data", quantized=True, bits=4 if args.bits4 else 8)
-    seg_req = mx.SegmentedAllReduce(d, [per] * nt, dtype=args.dtype, group="data",
-                                    post_scale=1.0 / size,
-                                    compression="int4" if args.bits4 else "int8")
+    if args.exact:
+        flat_req = mx.PersistentRequest(d, "all_reduce", per * nt, dtype=args.dtype, op="sum",
+                                        group="data")
+        seg_req = mx.SegmentedAllReduce(d, counts, dtype=args.dtype, group="data",
+                                        post_scale=1.0 / size, compression=None)
+    else:
+        flat_req = mx.PersistentRequest(d, "all_reduce", per * nt, dtype=args.dtype, op="sum",
+                                        group="data", quantized=True,
+                                        bits=4 if args.bits4 else 8)
+        seg_req = mx.SegmentedAllReduce(d, counts, dtype=args.dtype, group="data",
+                                        post_scale=1.0 / size,
+                                        compression="int4" if args.bits4 else "int8")
 
     def flat():
         buf = torch.cat([g.reshape(-1) for g in grads])
@@ -184,9 +283,9 @@ def bucket(args):
         flat_req.wait()
         buf /= size
         off = 0
-        for g in grads:
-            g.copy_(buf[off:off + per])
-            off += per
+        for g, n in zip(grads, counts):
+            g.copy_(buf[off:off + n])
+            off += n
 
     def segments():
         seg_req.start(grads)
@@ -215,7 +314,8 @@ def bucket(args):
         for k, fn in variants.items():
             times[k].append(timed(fn))
     if rank == 0:
-        res = {"config": "ddp-bucket", "bits": 4 if args.bits4 else 8, "dtype": args.dtype,
+        res = {"config": "ddp-bucket", "bits": 0 if args.exact else 4 if args.bits4 else 8,
+               "dtype": args.dtype,
                "bucket_mib": per * nt * es >> 20,
                "tensors": nt, "world": size, "iters": args.iters, "rounds": args.rounds,
                **{f"{k}_ms": _stats(v) for k, v in times.items()}}
@@ -238,8 +338,13 @@ def main():
     ap.add_argument("--bits4", action="store_true", help="the int4 wire")
     ap.add_argument("--path", default=None, choices=["fast", "generic"],
                     help="with --bits4 in kernels mode: the int4 list kernels' path")
+    ap.add_argument("--exact", action="store_true", help="the exact list request")
+    ap.add_argument("--tensors", type=int, default=64,
+                    help="bucket mode: tensors in the bucket (64 equal, else ragged)")
     args = ap.parse_args()
-    {"kernels": kernels, "bucket": bucket}[args.mode](args)
+    if args.exact and args.bits4:
+        ap.error("--exact and --bits4 exclude each other")
+    {"kernels": kernels_exact if args.exact else kernels, "bucket": bucket}[args.mode](args)
 
 
 if __name__ == "__main__":

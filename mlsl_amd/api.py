@@ -573,16 +573,28 @@ class SegmentedAllReduce:
     times ``float32(post_scale)``. It runs two_shot only: ar_algo=None means
     two_shot whatever MLSL_QUANT_AR_ALGO says, "ring" is refused, as are more
     than 8 ranks and a block that is no multiple of 8.
+    compression=None is the EXACT all_reduce of the list (dtype "f32", "bf16"
+    or "f16"; ar_algo must be None): bit for bit the flat exact all_reduce of
+    the concatenation, every element then times ``float32(post_scale)`` rounded
+    once into the dtype (``post_scale=1`` leaves the sum's bits). One kernel
+    gathers the tensors into a flat buffer, the flat all_reduce runs in place on
+    it with the transport and algorithm that count would get anyway, and a
+    second kernel scales it back into the tensors. The price: the request
+    keeps that buffer, ``sum(counts)`` elements, for its lifetime (the
+    compressed forms keep their smaller wire and a residual instead).
     Refused at creation: any other dtype, an empty list, a zero count, a
     compression plugin. One bucket of DistributedData(compression="int8" or
-    "int4") is one such request."""
+    "int4"), or of DistributedData(grads="in_place"), is one such request."""
 
     def __init__(self, dist, counts, dtype="f32", group="global", ar_algo=None,
                  post_scale=1.0, compression="int8"):
         if ar_algo is not None and ar_algo not in QUANT_AR_ALGO:
             raise ValueError(f"ar_algo={ar_algo!r}: expected None, 'ring' or 'two_shot'")
-        if compression not in ("int8", "int4"):
-            raise ValueError(f"compression={compression!r}: expected 'int8' or 'int4'")
+        if compression not in (None, "int8", "int4"):
+            raise ValueError(f"compression={compression!r}: expected None, 'int8' or 'int4'")
+        if compression is None and ar_algo is not None:
+            raise ValueError("ar_algo= selects the quantized all_reduce's algorithm: "
+                             "it needs compression='int8' or 'int4'")
         L = lib()
         if not hasattr(L, "_segments_declared"):
             P = ctypes.POINTER
@@ -593,6 +605,9 @@ class SegmentedAllReduce:
                 c_void_p, P(c_size_t), c_size_t, c_int, c_int, c_int, ctypes.c_float, c_int,
                 P(c_void_p)]
             L.mlsl_persistent_all_reduce_quantized_segments_bits.restype = c_int
+            L.mlsl_persistent_all_reduce_segments.argtypes = [
+                c_void_p, P(c_size_t), c_size_t, c_int, c_int, ctypes.c_float, P(c_void_p)]
+            L.mlsl_persistent_all_reduce_segments.restype = c_int
             L.mlsl_request_start_segments.argtypes = [c_void_p, P(c_void_p), c_size_t]
             L.mlsl_request_wait.argtypes = [c_void_p, P(c_void_p)]
             L.mlsl_request_test.argtypes = [c_void_p, P(c_int)]
@@ -607,7 +622,11 @@ class SegmentedAllReduce:
         self.nseg = len(counts)
         h = c_void_p()
         algo = -1 if ar_algo is None else QUANT_AR_ALGO[ar_algo]
-        if compression == "int4":
+        if compression is None:
+            check(L.mlsl_persistent_all_reduce_segments(
+                dist._h, _sizes(counts), len(counts), DTYPE[dtype], GROUP[group], post_scale,
+                ctypes.byref(h)))
+        elif compression == "int4":
             # "ring" raises the library's message
             check(L.mlsl_persistent_all_reduce_quantized_segments_bits(
                 dist._h, _sizes(counts), len(counts), DTYPE[dtype], GROUP[group], algo,

@@ -369,6 +369,22 @@ int mlsl_persistent_all_reduce_quantized_segments_bits(mlsl_distribution d,
     C_CATCH
 }
 
+int mlsl_persistent_all_reduce_segments(mlsl_distribution d, const size_t* counts, size_t nseg,
+                                        mlsl_data_type dt, mlsl_group g, float post_scale,
+                                        mlsl_request* out) {
+    C_TRY
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16 || DT(dt) == DataType::F16,
+               "all_reduce over a tensor list supports f32/bf16/f16 only");
+    MLSL_CHECK(nseg > 0 && counts != nullptr,
+               "all_reduce over a tensor list needs at least one tensor (nseg == 0)");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    // no SetCompression: the exact member of the family
+    r->AddAllReduceSegments(std::vector<size_t>(counts, counts + nseg), post_scale);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
 int mlsl_request_start_segments(mlsl_request req, void* const* ptrs, size_t nseg) {
     C_TRY static_cast<CommRequest*>(req)->StartSegments(ptrs, nseg);
     C_CATCH

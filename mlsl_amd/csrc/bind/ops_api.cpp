@@ -386,6 +386,67 @@ int mlsl_host_dequantize_scatter4(const void* wire, void* const* ptrs, const siz
     OPS_CATCH
 }
 
+// The exact pair: the list copied into `flat`, and `flat` scaled back into it.
+int mlsl_hip_gather_list(const void* const* ptrs, const size_t* counts, size_t nseg,
+                         void* flat, int dt) {
+    OPS_TRY size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "gather-list");
+    DevSegTables tab(offs, ptrs);
+    LaunchGatherList(tab.ptrs, tab.offs, nseg, flat, count, static_cast<DataType>(dt), nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_scatter_scale_list(const void* flat, void* const* ptrs, const size_t* counts,
+                                size_t nseg, int dt, float post_scale) {
+    OPS_TRY size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "scatter-scale-list");
+    DevSegTables tab(offs, ptrs);
+    LaunchScatterScaleList(flat, tab.ptrs, tab.offs, nseg, count, static_cast<DataType>(dt),
+                           post_scale, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_gather_list_tables(const void* const* dev_ptrs, const uint64_t* dev_offs,
+                                size_t nseg, void* flat, size_t count, int dt) {
+    OPS_TRY LaunchGatherList(dev_ptrs, dev_offs, nseg, flat, count, static_cast<DataType>(dt),
+                             nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_scatter_scale_list_tables(const void* flat, void* const* dev_ptrs,
+                                       const uint64_t* dev_offs, size_t nseg, size_t count,
+                                       int dt, float post_scale) {
+    OPS_TRY LaunchScatterScaleList(flat, dev_ptrs, dev_offs, nseg, count,
+                                   static_cast<DataType>(dt), post_scale, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_list_elems_per_trip(int dt, size_t* out) {
+    OPS_TRY* out = ListElemsPerTrip(static_cast<DataType>(dt));
+    OPS_CATCH
+}
+
+int mlsl_host_gather_list(const void* const* ptrs, const size_t* counts, size_t nseg,
+                          void* flat, int dt) {
+    OPS_TRY size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "gather-list");
+    HostGatherList(ptrs, offs.data(), nseg, flat, count, static_cast<DataType>(dt));
+    OPS_CATCH
+}
+
+int mlsl_host_scatter_scale_list(const void* flat, void* const* ptrs, const size_t* counts,
+                                 size_t nseg, int dt, float post_scale) {
+    OPS_TRY size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "scatter-scale-list");
+    HostScatterScaleList(flat, ptrs, offs.data(), nseg, count, static_cast<DataType>(dt),
+                         post_scale);
+    OPS_CATCH
+}
+
 // quantize-gather of the list padded with zeros to nshards * shard elements,
 // shard by shard: wire j at wire + j * wire_stride, the residual flat.
 int mlsl_hip_quantize_gather_shards(const void* const* ptrs, const size_t* counts, size_t nseg,

@@ -366,6 +366,12 @@ void DeviceSetupRequest(CommRequest* req, DeviceReqState& st) {
         HIP_CHECKD(hipHostMalloc(&pin, nseg * sizeof(void*)));
         st.seg_ptrs_pin = static_cast<void**>(pin);
     }
+    if (req->SegmentedExact()) {
+        // the flat buffer the gather fills, the allreduce runs in place on and
+        // the scatter reads: the staged-recv slot, sized once, here
+        st.stage_recv_bytes = req->MessageBytes();
+        st.stage_recv = Context::Get().Device()->AllocDevice(st.stage_recv_bytes);
+    }
 }
 
 namespace {
@@ -792,9 +798,24 @@ void GrowBuffer(HipRuntime* rt, void*& buf, size_t& have, size_t need, bool pinn
     have = need;
 }
 
+// The device pointer table of a request over nseg tensors (after the offsets).
+void** SegPtrsDev(const DeviceReqState& st, size_t nseg) {
+    return reinterpret_cast<void**>(static_cast<uint8_t*>(st.seg_dev) +
+                                    (nseg + 1) * sizeof(uint64_t));
+}
+
 // Stage the result out: D2H into the pinned bounce (pageable user memory) or
 // straight into the user's registered buffer.
 void EnqueueUnstage(CommRequest* req, DeviceReqState& st, hipStream_t s) {
+    if (req->SegmentedExact()) {
+        // the exact allreduce over a list: its flat buffer, scaled, back into
+        // the tensors through the tables StageInSegments uploaded
+        const size_t nseg = req->SegPtrs().size();
+        LaunchScatterScaleList(st.stage_recv, SegPtrsDev(st, nseg),
+                               static_cast<const uint64_t*>(st.seg_dev), nseg,
+                               req->Spec().count, req->Dtype(), req->PostScale(), s);
+        return;
+    }
     HIP_CHECKD(hipMemcpyAsync(
         st.unstage_pending ? st.pin_recv : static_cast<void*>(req->UserRecvBuf()),
         st.stage_recv, st.unstage_bytes, hipMemcpyDeviceToHost, s));
@@ -914,6 +935,28 @@ bool StageIn(CommRequest* req, HipRuntime* rt, GroupComms& gc, DeviceReqState& s
     req->SetDeviceBuffers(s_host ? static_cast<const uint8_t*>(st.stage_send) : nullptr,
                           r_host ? static_cast<uint8_t*>(st.stage_recv) : nullptr);
     return s_host || r_host;
+}
+
+// StageIn of the exact allreduce over a tensor list: the "host buffer" is the
+// list, the mover a kernel. This start's pointers go up as in IssueCompressed,
+// the gather fills the request's flat buffer on the base stream, the channel
+// streams order after it, and the allreduce is pointed at the buffer in place.
+// The result leaves through EnqueueUnstage, after the channels joined.
+bool StageInSegments(CommRequest* req, GroupComms& gc, DeviceReqState& st, hipStream_t base_s) {
+    const size_t nseg = req->SegPtrs().size();
+    void** seg_ptrs = SegPtrsDev(st, nseg);
+    // the last start was waited for, so the pinned mirror is free
+    std::memcpy(st.seg_ptrs_pin, req->SegPtrs().data(), nseg * sizeof(void*));
+    HIP_CHECKD(hipMemcpyAsync(seg_ptrs, st.seg_ptrs_pin, nseg * sizeof(void*),
+                              hipMemcpyHostToDevice, base_s));
+    LaunchGatherList(seg_ptrs, static_cast<const uint64_t*>(st.seg_dev), nseg, st.stage_recv,
+                     req->Spec().count, req->Dtype(), base_s);
+    FanOutStream0(gc, st);
+    st.recv_staged = true;
+    st.unstage_pending = false;
+    uint8_t* flat = static_cast<uint8_t*>(st.stage_recv);
+    req->SetDeviceBuffers(flat, flat);
+    return true;
 }
 
 // Order the priority lane after the producers and any staging H2D:
@@ -1116,7 +1159,8 @@ bool DeviceAdvanceRequest(CommRequest* req, DeviceReqState& st) {
         if (ReplayGraph(req, gc, st)) return AllEventsDone(st);
     }
 
-    const bool staged = StageIn(req, rt, gc, st, ic.base_s);
+    const bool staged = req->SegmentedExact() ? StageInSegments(req, gc, st, ic.base_s)
+                                              : StageIn(req, rt, gc, st, ic.base_s);
     ic.prio = cfg.msg_priority &&
               (gc.prio_comm || (ic.p2p && gc.prio_stream)) &&
               req->MessageBytes() >= cfg.msg_priority_threshold;

@@ -437,6 +437,114 @@ void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64
     }
 }
 
+namespace {
+
+// IEEE binary16 <-> float, round to nearest even; a NaN becomes the quiet NaN
+// of its sign (the device's conversions keep other payload bits: a NaN that
+// goes through a product compares as NaN, not bit for bit).
+inline float F16F(uint16_t h) {
+    const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16;
+    uint32_t exp = (h >> 10) & 0x1f, man = h & 0x3ffu, u;
+    if (exp == 0x1f) {
+        u = sign | 0x7f800000u | (man << 13);
+    } else if (exp != 0) {
+        u = sign | ((exp + 112) << 23) | (man << 13);
+    } else if (man == 0) {
+        u = sign;
+    } else {
+        // subnormal: normalise
+        exp = 113;
+        while (!(man & 0x400u)) {
+            man <<= 1;
+            --exp;
+        }
+        u = sign | (exp << 23) | ((man & 0x3ffu) << 13);
+    }
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+inline uint16_t F32H(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    const uint16_t sign = static_cast<uint16_t>((u >> 16) & 0x8000u);
+    const uint32_t a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return sign | 0x7e00u;
+    if (a >= 0x477ff000u) return sign | 0x7c00u;   // rounds to 2^16 or above: inf
+    if (a < 0x33000001u) return sign;              // at most half the least subnormal
+    uint32_t man = (a & 0x7fffffu) | 0x800000u;
+    const int exp = static_cast<int>(a >> 23) - 112;   // binary16 biased exponent
+    // bits of man dropped: 13 for a normal result, more for a subnormal one
+    const int shift = exp >= 1 ? 13 : 14 - exp;
+    uint32_t r = man >> shift;
+    const uint32_t rem = man & ((1u << shift) - 1), half = 1u << (shift - 1);
+    if (rem > half || (rem == half && (r & 1))) ++r;
+    // a normal result carries the implicit bit in r: adding (exp - 1) << 10
+    // puts the exponent in, and a mantissa carry bumps it by itself
+    return sign | static_cast<uint16_t>(exp >= 1 ? r + (static_cast<uint32_t>(exp - 1) << 10) : r);
+}
+
+// F32B adds its rounding bias to a NaN too and can carry it into infinity
+inline uint16_t F32BNan(float f) {
+    if (std::isnan(f)) return std::signbit(f) ? 0xffc0 : 0x7fc0;
+    return F32B(f);
+}
+
+void CheckListTables(const void* ptrs, const uint64_t* offs, size_t nseg, size_t count,
+                     DataType dt, const void* flat, const char* where) {
+    if (dt != DataType::F32 && dt != DataType::BF16 && dt != DataType::F16)
+        MLSL_THROW(std::string(where) + " supports f32/bf16/f16 only");
+    MLSL_CHECK(nseg >= 1, std::string(where) + " takes at least one segment");
+    MLSL_CHECK(ptrs != nullptr && offs != nullptr && flat != nullptr,
+               std::string(where) + ": null segment table or flat buffer");
+    MLSL_CHECK(offs[0] == 0 && offs[nseg] == count,
+               std::string(where) + ": offsets do not run from 0 to count");
+    for (size_t j = 0; j < nseg; ++j)
+        MLSL_CHECK(offs[j + 1] > offs[j],
+                   std::string(where) + ": segment " + std::to_string(j) + " is empty");
+}
+
+}  // namespace
+
+void HostGatherList(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                    void* flat, size_t count, DataType dt) {
+    CheckListTables(seg_ptrs, seg_offs, nseg, count, dt, flat, "gather-list");
+    const size_t es = DtypeSize(dt);
+    SegCursor cur{seg_offs, nseg};
+    uint8_t* out = static_cast<uint8_t*>(flat);
+    for (size_t i = 0; i < count; ++i) {
+        const size_t k = cur.Seek(i);
+        std::memcpy(out + i * es, static_cast<const uint8_t*>(seg_ptrs[cur.s]) + k * es, es);
+    }
+}
+
+void HostScatterScaleList(const void* flat, void* const* seg_ptrs, const uint64_t* seg_offs,
+                          size_t nseg, size_t count, DataType dt, float post_scale) {
+    CheckListTables(seg_ptrs, seg_offs, nseg, count, dt, flat, "scatter-scale-list");
+    const size_t es = DtypeSize(dt);
+    SegCursor cur{seg_offs, nseg};
+    const uint8_t* in = static_cast<const uint8_t*>(flat);
+    for (size_t i = 0; i < count; ++i) {
+        const size_t k = cur.Seek(i);
+        uint8_t* o = static_cast<uint8_t*>(seg_ptrs[cur.s]) + k * es;
+        if (post_scale == 1.0f) {
+            std::memcpy(o, in + i * es, es);   // the bits, NaN payloads included
+        } else if (dt == DataType::F32) {
+            float v;
+            std::memcpy(&v, in + i * es, 4);
+            v *= post_scale;
+            std::memcpy(o, &v, 4);
+        } else {
+            uint16_t h;
+            std::memcpy(&h, in + i * es, 2);
+            h = dt == DataType::BF16 ? F32BNan(Bf16F(h) * post_scale)
+                                     : F32H(F16F(h) * post_scale);
+            std::memcpy(o, &h, 2);
+        }
+    }
+}
+
 const QuantPluginApi* LoadQuantPlugin(const QuantParams& qp) {
     if (qp.lib_path.empty()) return nullptr;
     static std::mutex mu;

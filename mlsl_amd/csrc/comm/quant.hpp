@@ -95,6 +95,18 @@ void HostDequantizeScatter(const void* wire, void* const* seg_ptrs, const uint64
                            size_t nseg, size_t count, size_t block, DataType dt,
                            float post_scale, bool round_first = false, int bits = 8);
 
+// The exact pair over the same tables, f32/bf16/f16: the twins of
+// LaunchGatherList and LaunchScatterScaleList (hip/kernels.hpp), in plain loops.
+// Gather: flat[i] = V[i], the bits. Scatter: V[i] = Encode(Decode(flat[i]) *
+// post_scale), one float32 product and one rounding to nearest even into the
+// element type; at post_scale == 1.0f the bits. A NaN that goes through the
+// product comes out as the quiet NaN of its sign in bf16/f16 (the device keeps
+// other payload bits): NaN for NaN, everything else bit for bit.
+void HostGatherList(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                    void* flat, size_t count, DataType dt);
+void HostScatterScaleList(const void* flat, void* const* seg_ptrs, const uint64_t* seg_offs,
+                          size_t nseg, size_t count, DataType dt, float post_scale);
+
 // dlopen'd compression plugin (reference quant/quant.c ABI — Intel
 // DL-comp style). Loaded once per lib_path; used by the HOST compressed
 // path when QuantParams.lib_path is set. Signatures quant/quant.c:57-65.

@@ -561,13 +561,14 @@ void CommRequest::Setup() {
         MLSL_CHECK(comp_ == Compression::QUANT_INT8,
                    "reduce_scatter over a tensor list exists quantized only "
                    "(SetCompression(QUANT_INT8))");
+    } else if (SegmentedExact()) {
+        MLSL_CHECK(dtype_ == DataType::F32 || dtype_ == DataType::BF16 ||
+                       dtype_ == DataType::F16,
+                   "all_reduce over a tensor list supports f32/bf16/f16 only");
     } else if (Segmented()) {
         // never an exact allreduce of the list behind the caller's back
         MLSL_CHECK(dtype_ == DataType::F32 || dtype_ == DataType::BF16,
                    "quantized all_reduce over a tensor list supports f32/bf16 only");
-        MLSL_CHECK(comp_ == Compression::QUANT_INT8,
-                   "all_reduce over a tensor list exists quantized only "
-                   "(SetCompression(QUANT_INT8))");
     }
     BuildChunks();
     // after BuildChunks, whose two-shot and direct refusals come first with
@@ -585,6 +586,7 @@ void CommRequest::Setup() {
     } else {
         for (auto& ce : chunks_)
             ce.tmp.assign(Compressed() ? ce.qplan.bytes : ce.sch.tmp_bytes, 0);
+        if (SegmentedExact()) seg_flat_.assign(MessageBytes(), 0);
     }
     setup_done_ = true;
 }
@@ -666,7 +668,11 @@ void CommRequest::StartSegments(void* const* ptrs, size_t nseg) {
     // refused before anything of the last start is overwritten
     if (Context::Get().DeviceMode()) DeviceCheckSegmentPointers(ptrs, nseg);
     seg_ptrs_.assign(ptrs, ptrs + nseg);
-    StartCommon(nullptr, nullptr);
+    seg_gathered_ = false;
+    // exact on the host: the flat allreduce runs in place on the request's own
+    // buffer (in device mode the issue path puts its device buffer there)
+    uint8_t* flat = seg_flat_.empty() ? nullptr : seg_flat_.data();
+    StartCommon(flat, flat);
 }
 
 void CommRequest::StartCommon(const void* sbuf, void* rbuf) {
@@ -736,6 +742,7 @@ void* CommRequest::Wait() {
         MLSL_THROW("request failed: " + error_);
     state_.store(ReqState::IDLE, std::memory_order_release);
     if (chunks_.empty()) return rbuf_;
+    if (SegmentedExact()) return nullptr;  // the result lies in the tensors
     if (Compressed()) return rbuf_;  // dequantized into the user recv buffer
     const BufRef& res = chunks_[0].sch.result;
     switch (res.space) {
@@ -783,6 +790,12 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
     bool all_done = true;
 
     const bool compressed = Compressed();
+    if (SegmentedExact() && !seg_gathered_) {
+        // the tensors into the flat buffer every chunk reads
+        HostGatherList(seg_ptrs_.data(), seg_offs_.data(), seg_ptrs_.size(), seg_flat_.data(),
+                       spec_.count, dtype_);
+        seg_gathered_ = true;
+    }
     for (auto& ce : chunks_) {
         if (ce.finished) continue;
         const uint8_t* sbase = sbuf_ + ce.elem_off * es;
@@ -959,6 +972,9 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
         }
         if (!ce.finished) all_done = false;
     }
+    if (all_done && SegmentedExact())
+        HostScatterScaleList(seg_flat_.data(), seg_ptrs_.data(), seg_offs_.data(),
+                             seg_ptrs_.size(), spec_.count, dtype_, post_scale_);
     return all_done;
 }
 

@@ -101,6 +101,11 @@ class CommRequest {
     // they lie (quant.hpp, HostQuantizeGather / HostDequantizeScatter), and
     // the finish multiplies by post_scale. Needs SetCompression(QUANT_INT8)
     // on f32/bf16 without a plugin, or Setup() fails; runs with StartSegments.
+    // Without SetCompression it is the exact allreduce of the list (f32/bf16/
+    // f16): the request owns one flat buffer of the concatenation's size, a
+    // gather kernel fills it (quant.hpp, HostGatherList), the flat exact
+    // allreduce runs in place on it, chunks, transports and algorithms as for
+    // AddAllReduce of that count, and a scatter writes flat * post_scale back.
     void AddAllReduceSegments(const std::vector<size_t>& counts, float post_scale);
     // The quantized reduce-scatter (SUM) over a list of tensors of counts[j] >=
     // 1 elements: bit for bit AddReduceScatter(shard) + SetCompression on V',
@@ -216,6 +221,10 @@ class CommRequest {
     // description), this start's nseg pointers, the allreduce finish's factor.
     bool Segmented() const { return !seg_offs_.empty(); }
     bool SegmentedReduceScatter() const { return Segmented() && seg_rs_; }
+    // the exact allreduce over a list: gather, flat allreduce, scatter
+    bool SegmentedExact() const {
+        return Segmented() && !seg_rs_ && comp_ == Compression::NONE;
+    }
     const std::vector<uint64_t>& SegOffs() const { return seg_offs_; }
     const std::vector<void*>& SegPtrs() const { return seg_ptrs_; }
     float PostScale() const { return post_scale_; }
@@ -245,6 +254,8 @@ class CommRequest {
     bool seg_rs_ = false;              // AddReduceScatterSegments
     std::vector<void*> seg_ptrs_;      // per StartSegments
     float post_scale_ = 1.0f;
+    std::vector<uint8_t> seg_flat_;    // SegmentedExact on the host: the flat buffer
+    bool seg_gathered_ = false;        // ... and whether this start filled it
 
     std::vector<ChunkExec> chunks_;
     size_t total_tmp_bytes_ = 0;

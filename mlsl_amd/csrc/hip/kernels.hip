@@ -2742,6 +2742,207 @@ void LaunchDequantizeScatter4(const void* wire, void* const* seg_ptrs,
     HIP_CHECK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------
+// The exact members of the list family: the concatenation V of a list of
+// tensors copied into one flat buffer, and the flat buffer scaled back into
+// the tensors. Same two device tables as above.
+//
+// Split of work: a wave owns a fixed tile of `flat`, kListTileBytes, so the
+// flat side of a tile always starts 16-byte aligned. The wave finds the
+// tensor of the tile's first element by SegCursor's bisection, then walks the
+// tile's runs, a run being the intersection of the tile with one tensor; from
+// one run to the next the cursor steps to the next table entry, no bisection.
+// All of that is uniform across the wave and stays in scalar registers.
+//
+// The access width is chosen per run, uniform, from the difference between the
+// tensor address and the flat address of the run, because that difference, not
+// the tensor's own alignment, decides whether both sides can be accessed at
+// one width: 0 mod 16 bytes takes 16-byte accesses on both sides, 0 mod 4
+// dword accesses (lane-strided, 256 contiguous bytes an instruction), anything
+// else (2-byte types only) halfword accesses. The up to W / sizeof(T) - 1
+// elements before the first and after the last W-aligned address of a run go
+// one element per lane. QuantizeSegBlock's scheme, where a block that is not
+// wholly inside one tensor at a 16-byte aligned address walks the table
+// element by element, is what this replaces: after the first tensor of odd
+// length nearly every tensor of a model disagrees with its offset in `flat`
+// modulo 16, and those lists still move at dword width here.
+//
+// A tile with more than kListMaxRuns runs (hundreds of tensors of a few
+// elements) hands its remainder to the lanes: each walks the table forward on
+// its own (LaneSeg), one element an access.
+//
+// Loads are nontemporal and stores plain in both kernels. The gather reads
+// gradients nobody reads again before they are overwritten and writes the
+// buffer the transport reads next; the scatter reads that buffer for the last
+// time and writes the tensors the optimizer reads next.
+
+namespace {
+
+constexpr int kListMaxRuns = 8;
+static_assert(kListWavesPerTrip == static_cast<size_t>(kMaxGrid) * (kBlock / 64),
+              "ListElemsPerTrip must state what WaveGrid's cap covers");
+
+template <int W> struct ListWord;
+template <> struct ListWord<16> { using type = uint4_ev; };
+template <> struct ListWord<4> { using type = uint32_t; };
+template <> struct ListWord<2> { using type = uint16_t; };
+
+// The sizeof(V) / sizeof(T) elements held by v, each Encode(Decode(x) * s);
+// without SCALE the bits as they are (NaN payloads and -0 included). The
+// product is a float32 in a register of its own before it is rounded: left to
+// itself the compiler folds an f16 product and its rounding into one
+// v_fma_mixlo_f16, whose result was seen to differ from a v_mul_f32 followed
+// by a conversion (and from the 16-byte path, which gets those two).
+template <typename T, bool SCALE, typename V>
+__device__ __forceinline__ V ListScale(V v, float s) {
+    if constexpr (SCALE) {
+        constexpr int N = sizeof(V) / sizeof(T);
+        T e[N];
+        __builtin_memcpy(e, &v, sizeof(V));
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            float p = Decode(e[j]) * s;
+            if constexpr (sizeof(T) == 2) asm volatile("" : "+v"(p));
+            e[j] = Encode<T>(p);
+        }
+        __builtin_memcpy(&v, e, sizeof(V));
+    }
+    return v;
+}
+
+// n >= 1 elements from src to dst at access width W bytes; the two addresses
+// agree modulo W. Four accesses of a lane are in flight before the first store.
+template <typename T, int W, bool SCALE>
+__device__ __forceinline__ void ListMoveRunW(const T* src, T* dst, size_t n, float s,
+                                             int lane) {
+    using E = typename ListWord<sizeof(T)>::type;
+    using V = typename ListWord<W>::type;
+    constexpr size_t G = W / sizeof(T);
+    auto one = [&](size_t i) {
+        reinterpret_cast<E*>(dst)[i] = ListScale<T, SCALE>(
+            __builtin_nontemporal_load(reinterpret_cast<const E*>(src) + i), s);
+    };
+    size_t head = 0;
+    if constexpr (G > 1) {
+        head = ((0 - reinterpret_cast<uintptr_t>(dst)) & (W - 1)) / sizeof(T);
+        if (head > n) head = n;
+        if (static_cast<size_t>(lane) < head) one(lane);
+    }
+    const size_t nvec = (n - head) / G;
+    const V* sv = reinterpret_cast<const V*>(src + head);
+    V* dv = reinterpret_cast<V*>(dst + head);
+    for (size_t i = lane; i < nvec; i += 256) {
+        V v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + 64 * k < nvec) v[k] = __builtin_nontemporal_load(sv + i + 64 * k);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + 64 * k < nvec) dv[i + 64 * k] = ListScale<T, SCALE>(v[k], s);
+    }
+    if constexpr (G > 1) {
+        const size_t tail = head + nvec * G + lane;
+        if (tail < n) one(tail);
+    }
+}
+
+// One run: n elements of one tensor at `tens`, their place in the flat buffer
+// at `flat`. GATHER copies tensor to flat, otherwise flat goes to the tensor.
+template <typename T, bool GATHER, bool SCALE>
+__device__ __forceinline__ void ListMoveRun(T* tens, T* flat, size_t n, float s, int lane) {
+    const uintptr_t d = reinterpret_cast<uintptr_t>(tens) - reinterpret_cast<uintptr_t>(flat);
+    const T* src = GATHER ? tens : flat;
+    T* dst = GATHER ? flat : tens;
+    if ((d & 15) == 0) ListMoveRunW<T, 16, SCALE>(src, dst, n, s, lane);
+    else if (sizeof(T) == 4 || (d & 3) == 0) ListMoveRunW<T, 4, SCALE>(src, dst, n, s, lane);
+    else ListMoveRunW<T, sizeof(T), SCALE>(src, dst, n, s, lane);
+}
+
+template <typename T, bool GATHER, bool SCALE>
+__global__ void ListMoveKernel(T* const* __restrict__ ptrs, SegTable tab, T* flat,
+                               size_t count, float post_scale) {
+    using E = typename ListWord<sizeof(T)>::type;
+    constexpr size_t kTile = kListTileBytes / sizeof(T);
+    SegCursor<T> cur;
+    ForEachWaveBlock((count + kTile - 1) / kTile, [&](size_t vtile, int lane) {
+        const size_t begin = WaveUniform(vtile) * kTile;
+        const size_t end = min(count, begin + kTile);
+        cur.Seek(tab, ptrs, begin);
+        size_t e = begin;
+        for (int runs = 0; e < end; ++runs) {
+            if (e >= cur.hi) {
+                // the next tensor; the table's last entry bounds the walk
+                // whatever `count` says
+                if (cur.seg + 1 >= tab.nseg) return;
+                ++cur.seg;
+                cur.lo = cur.hi;
+                cur.hi = tab.offs[cur.seg + 1];
+                cur.ptr = ptrs[cur.seg];
+            }
+            if (runs == kListMaxRuns) {
+                LaneSeg<T> ls(cur);
+                for (size_t i = e + lane; i < end; i += 64) {
+                    E* t = reinterpret_cast<E*>(ls.At(tab, ptrs, i));
+                    E* f = reinterpret_cast<E*>(flat + i);
+                    if constexpr (GATHER) *f = __builtin_nontemporal_load(t);
+                    else *t = ListScale<T, SCALE>(__builtin_nontemporal_load(f), post_scale);
+                }
+                return;
+            }
+            const size_t run_end = min(static_cast<size_t>(cur.hi), end);
+            ListMoveRun<T, GATHER, SCALE>(cur.ptr + (e - cur.lo), flat + e, run_end - e,
+                                          post_scale, lane);
+            e = run_end;
+        }
+    });
+}
+
+template <bool GATHER>
+void LaunchListMove(void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg, void* flat,
+                    size_t count, DataType dt, float post_scale, hipStream_t stream,
+                    const char* where) {
+    if (dt != DataType::F32 && dt != DataType::BF16 && dt != DataType::F16)
+        MLSL_THROW(std::string(where) + " supports f32/bf16/f16 only");
+    MLSL_CHECK(nseg >= 1 && nseg <= 0xffffffffull && count >= nseg,
+               std::string(where) + " takes at least one segment of at least one element");
+    MLSL_CHECK(seg_ptrs != nullptr && seg_offs != nullptr,
+               std::string(where) + ": null segment table");
+    MLSL_CHECK(flat != nullptr && (reinterpret_cast<uintptr_t>(flat) & 15) == 0,
+               std::string(where) + ": the flat buffer must be 16-byte aligned");
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const dim3 grid = WaveGrid(NumBlocks(count * DtypeSize(dt), kListTileBytes));
+    auto launch = [&](auto* elem) {
+        using T = std::remove_pointer_t<decltype(elem)>;
+        // the gather never scales; the scatter at 1.0f copies the bits
+        DispatchBool(!GATHER && post_scale != 1.0f, [&](auto sc) {
+            ListMoveKernel<T, GATHER, decltype(sc)::value><<<grid, dim3(kBlock), 0, stream>>>(
+                reinterpret_cast<T* const*>(seg_ptrs), tab, static_cast<T*>(flat), count,
+                post_scale);
+        });
+    };
+    if (dt == DataType::F32) launch(static_cast<float*>(nullptr));
+    else if (dt == DataType::BF16) launch(static_cast<unsigned short*>(nullptr));
+    else launch(static_cast<__half*>(nullptr));
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+void LaunchGatherList(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                      void* flat, size_t count, DataType dt, hipStream_t stream) {
+    // the tensors are only read: the kernel's GATHER arm never stores through them
+    LaunchListMove<true>(const_cast<void* const*>(seg_ptrs), seg_offs, nseg, flat, count, dt,
+                         1.0f, stream, "gather-list");
+}
+
+void LaunchScatterScaleList(const void* flat, void* const* seg_ptrs, const uint64_t* seg_offs,
+                            size_t nseg, size_t count, DataType dt, float post_scale,
+                            hipStream_t stream) {
+    // flat is only read: the kernel's scatter arm never stores into it
+    LaunchListMove<false>(seg_ptrs, seg_offs, nseg, const_cast<void*>(flat), count, dt,
+                          post_scale, stream, "scatter-scale-list");
+}
+
 // --- IPC p2p transport (comm/p2p_transport.cpp) ---
 // Mailboxes are monotonically increasing u64 sequence counters in the
 // receiver's HBM window; the writer is a remote process on the same or a

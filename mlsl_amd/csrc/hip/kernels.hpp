@@ -197,6 +197,30 @@ void LaunchDequantizeScatter4(const void* wire, void* const* seg_ptrs,
                               size_t block_elems, DataType dt, float post_scale,
                               bool round_first, hipStream_t stream,
                               Quant4Path path = Quant4Path::AUTO);
+// The exact pair over the same tables, f32/bf16/f16 (anything else throws
+// "supports f32/bf16/f16 only"). Gather: flat[i] = V[i], the bits unchanged
+// (NaN payloads and -0 survive); the tensors are only read and nothing outside
+// flat[0, count) is written. Scatter: V[i] = Encode(Decode(flat[i]) *
+// post_scale), one float32 product and one rounding into the element type; at
+// post_scale == 1.0f the copy of the bits; flat is only read and no byte
+// outside the tensors is written. `flat` must be 16-byte aligned; the tensors
+// need their element's alignment only. A wave owns a fixed tile of `flat` and
+// picks 16-byte, dword or halfword accesses per run from the difference of the
+// two addresses (kernels.hip). The host twins (comm/quant.hpp) compute the same
+// bits.
+void LaunchGatherList(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                      void* flat, size_t count, DataType dt, hipStream_t stream);
+void LaunchScatterScaleList(const void* flat, void* const* seg_ptrs, const uint64_t* seg_offs,
+                            size_t nseg, size_t count, DataType dt, float post_scale,
+                            hipStream_t stream);
+// What one launch of either covers before its grid-stride loop takes a second
+// trip: kListWavesPerTrip waves (the grid's cap, asserted in kernels.hip) of
+// one kListTileBytes tile each.
+constexpr size_t kListTileBytes = 4096;   // 64 lanes x 16 bytes x 4 in flight
+constexpr size_t kListWavesPerTrip = 8192;
+inline size_t ListElemsPerTrip(DataType dt) {
+    return kListWavesPerTrip * (kListTileBytes / DtypeSize(dt));
+}
 
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,

@@ -177,6 +177,19 @@ int mlsl_persistent_all_reduce_quantized_segments_bits(mlsl_distribution d,
                                                        mlsl_data_type dt, mlsl_group g,
                                                        int algo, float post_scale, int bits,
                                                        mlsl_request* out);
+/* The exact all_reduce (SUM) over a list of nseg tensors of counts[j] >= 1
+ * elements, in place, f32/bf16/f16: bit for bit the flat exact all_reduce of
+ * their concatenation, every element then multiplied by post_scale in float
+ * and rounded once into the element type (post_scale == 1: the sum's bits).
+ * The request owns one buffer of sum(counts) elements for its lifetime: a
+ * kernel gathers the tensors into it, the flat all_reduce runs in place on it
+ * with whatever transport and algorithm that count would get, and a second
+ * kernel scales it back into the tensors. Started with
+ * mlsl_request_start_segments, with that call's rules: device pointers only
+ * in device mode, never graph-replayed, the list's length fixed at creation. */
+int mlsl_persistent_all_reduce_segments(mlsl_distribution d, const size_t* counts, size_t nseg,
+                                        mlsl_data_type dt, mlsl_group g, float post_scale,
+                                        mlsl_request* out);
 int mlsl_request_start_segments(mlsl_request req, void* const* ptrs, size_t nseg);
 int mlsl_persistent_reduce_scatter(mlsl_distribution d, size_t recv_count,
                                    mlsl_data_type dt, mlsl_reduction op, mlsl_group g,

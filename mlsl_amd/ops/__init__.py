@@ -97,6 +97,24 @@ def _lib():
                   "mlsl_hip_quantize_gather4_tables", "mlsl_hip_dequantize_scatter4_tables",
                   "mlsl_host_quantize_gather4", "mlsl_host_dequantize_scatter4"):
             getattr(L, n).restype = c.c_int
+        L.mlsl_hip_gather_list.argtypes = [c.POINTER(c.c_void_p), c.POINTER(c.c_size_t),
+                                           c.c_size_t, c.c_void_p, c.c_int]
+        L.mlsl_host_gather_list.argtypes = L.mlsl_hip_gather_list.argtypes
+        L.mlsl_hip_scatter_scale_list.argtypes = [c.c_void_p, c.POINTER(c.c_void_p),
+                                                  c.POINTER(c.c_size_t), c.c_size_t, c.c_int,
+                                                  c.c_float]
+        L.mlsl_host_scatter_scale_list.argtypes = L.mlsl_hip_scatter_scale_list.argtypes
+        L.mlsl_hip_gather_list_tables.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t,
+                                                  c.c_void_p, c.c_size_t, c.c_int]
+        L.mlsl_hip_scatter_scale_list_tables.argtypes = [c.c_void_p, c.c_void_p, c.c_void_p,
+                                                         c.c_size_t, c.c_size_t, c.c_int,
+                                                         c.c_float]
+        L.mlsl_hip_list_elems_per_trip.argtypes = [c.c_int, c.POINTER(c.c_size_t)]
+        for n in ("mlsl_hip_gather_list", "mlsl_host_gather_list",
+                  "mlsl_hip_scatter_scale_list", "mlsl_host_scatter_scale_list",
+                  "mlsl_hip_gather_list_tables", "mlsl_hip_scatter_scale_list_tables",
+                  "mlsl_hip_list_elems_per_trip"):
+            getattr(L, n).restype = c.c_int
         L.mlsl_hip_quantize_gather_tables.restype = c.c_int
         L.mlsl_hip_dequantize_scatter_tables.restype = c.c_int
         L.mlsl_hip_quantize_gather_shards.argtypes = [c.POINTER(c.c_void_p),
@@ -530,11 +548,62 @@ def dequantize_scatter_tables(wire, dev_ptrs, dev_offs, nseg, count, block=256, 
                                                     1 if round_first else 0))
 
 
+def gather_list(tensors, counts, flat, dtype=None):
+    """torch.cat(tensors) into `flat` in one launch, as raw bits (f32, bf16 or
+    f16; NaN payloads and -0 survive): `flat`, 16-byte aligned, gets sum(counts)
+    elements and nothing past them. The tensors (counts[j] elements each) are
+    only read and need their element's alignment only."""
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    fp, _ = _as_ptr_dtype(flat)
+    check(_lib().mlsl_hip_gather_list(ptrs, cnts, nseg, fp, DTYPE[dt]))
+
+
+def scatter_scale_list(flat, tensors, counts, dtype=None, post_scale=1.0):
+    """`flat` back into the list `tensors`, scaled: element i of the
+    concatenation becomes flat[i] * post_scale, one float32 product rounded once
+    into the element type; post_scale=1.0 copies the bits. `flat` is only read
+    and nothing outside the tensors is written."""
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    fp, _ = _as_ptr_dtype(flat)
+    check(_lib().mlsl_hip_scatter_scale_list(fp, ptrs, cnts, nseg, DTYPE[dt], post_scale))
+
+
+def gather_list_tables(dev_ptrs, dev_offs, nseg, count, flat, dtype="f32"):
+    """`gather_list` over tables in DEVICE memory; see `quantize_gather_tables`."""
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    op_, _ = _as_ptr_dtype(dev_offs)
+    fp, _ = _as_ptr_dtype(flat)
+    check(_lib().mlsl_hip_gather_list_tables(pp, op_, nseg, fp, count, DTYPE[dtype]))
+
+
+def scatter_scale_list_tables(flat, dev_ptrs, dev_offs, nseg, count, dtype="f32",
+                              post_scale=1.0):
+    """`scatter_scale_list` over tables in DEVICE memory; see
+    `quantize_gather_tables`."""
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    op_, _ = _as_ptr_dtype(dev_offs)
+    fp, _ = _as_ptr_dtype(flat)
+    check(_lib().mlsl_hip_scatter_scale_list_tables(fp, pp, op_, nseg, count, DTYPE[dtype],
+                                                    post_scale))
+
+
+def list_elems_per_trip(dtype):
+    """Elements one launch of `gather_list` or `scatter_scale_list` covers
+    before its grid-stride loop takes a second trip."""
+    n = ctypes.c_size_t(0)
+    check(_lib().mlsl_hip_list_elems_per_trip(DTYPE[dtype], ctypes.byref(n)))
+    return n.value
+
+
 _ELEM_BYTES = {"f32": 4, "bf16": 2}
+_LIST_ELEM_BYTES = {"f32": 4, "bf16": 2, "f16": 2}   # the exact pair takes f16 too
 
 
-def _host_seg_tables(arrays, counts, dtype, what):
-    if dtype not in _ELEM_BYTES:
+def _host_seg_tables(arrays, counts, dtype, what, elem_bytes=_ELEM_BYTES):
+    if dtype not in elem_bytes:
+        if elem_bytes is _LIST_ELEM_BYTES:
+            raise ValueError(f"dtype {dtype!r}: the exact list kernels support "
+                             "f32/bf16/f16 only")
         raise ValueError(f"dtype {dtype!r}: the list codec supports f32/bf16 only")
     if len(arrays) != len(counts):
         raise ValueError(f"{len(arrays)} {what} but {len(counts)} counts")
@@ -543,7 +612,7 @@ def _host_seg_tables(arrays, counts, dtype, what):
     for j, n in enumerate(counts):
         if int(n) < 1:
             raise ValueError(f"counts[{j}] = {n}: every segment needs at least one element")
-    eb = _ELEM_BYTES[dtype]
+    eb = elem_bytes[dtype]
     ptrs = (ctypes.c_void_p * len(arrays))(
         *[_host_buf(a, int(n) * eb, f"{what}[{j}]").value
           for j, (a, n) in enumerate(zip(arrays, counts))])
@@ -582,6 +651,24 @@ def host_dequantize_scatter(wire, arrays, counts, block=256, dtype="f32", post_s
     wp = _host_buf(wire, wire_bytes(total, block), "wire")
     check(_lib().mlsl_host_dequantize_scatter(wp, ptrs, cnts, nseg, block, DTYPE[dtype],
                                               post_scale, 1 if round_first else 0))
+
+
+def host_gather_list(arrays, counts, flat, dtype="f32"):
+    """Host twin of `gather_list` on numpy arrays: the same bits."""
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays",
+                                               _LIST_ELEM_BYTES)
+    fp = _host_buf(flat, total * _LIST_ELEM_BYTES[dtype], "flat")
+    check(_lib().mlsl_host_gather_list(ptrs, cnts, nseg, fp, DTYPE[dtype]))
+
+
+def host_scatter_scale_list(flat, arrays, counts, dtype="f32", post_scale=1.0):
+    """Host twin of `scatter_scale_list` on numpy arrays: the same bits, except
+    that a bf16/f16 NaN that goes through the product (post_scale != 1) comes
+    out as the quiet NaN of its sign."""
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays",
+                                               _LIST_ELEM_BYTES)
+    fp = _host_buf(flat, total * _LIST_ELEM_BYTES[dtype], "flat")
+    check(_lib().mlsl_host_scatter_scale_list(fp, ptrs, cnts, nseg, DTYPE[dtype], post_scale))
 
 
 def host_quantize_gather4(arrays, counts, wire, err=None, block=256, dtype="f32"):

@@ -29,6 +29,16 @@ compression="int4" is the same on the 4-bit wire (block / 2 + 8 bytes a block
 where int8 takes block + 8): the bits of a flat bits=4 request per bucket times
 float32(1/world). It runs the two-shot all_reduce only, so ar_algo is None or
 "two_shot" and the group has at most 8 ranks.
+
+grads="in_place" (default "copy", the same pair of words as ShardedOptimizer)
+gives every f32, bf16 or f16 bucket that has no compressed request one exact
+mx.SegmentedAllReduce(compression=None): a kernel gathers the gradients into
+the request's own flat buffer, the flat exact all_reduce runs on it, and a
+second kernel writes sum * float32(1/world) back into them, so again no
+torch.cat, no divide, no per-parameter copy, and finish_gradients() only
+waits. Each such bucket keeps a bucket-sized buffer for the wrapper's
+lifetime; gradients must be contiguous. The result is the flat request's sum
+times float32(1/world), where the default path divides by world.
 """
 import torch
 
@@ -37,7 +47,7 @@ import mlsl_amd as mx
 
 class DistributedData:
     def __init__(self, module, dist=None, bucket_mb=25, group="data",
-                 average=True, compression=None, ar_algo=None):
+                 average=True, compression=None, ar_algo=None, grads="copy"):
         if compression not in (None, "int8", "int4"):
             raise ValueError(f"compression={compression!r}: expected None, 'int8' or 'int4'")
         if ar_algo is not None and compression is None:
@@ -47,7 +57,10 @@ class DistributedData:
             raise ValueError("compression='int4' does not run ar_algo='ring': the ring "
                              "requantizes the partial sum on every hop, which at 4 bits "
                              "loses far more than at 8; name 'two_shot' or nothing")
+        if grads not in ("copy", "in_place"):
+            raise ValueError(f"grads={grads!r}: expected 'copy' or 'in_place'")
         self.compression = compression
+        self.grads = grads
         self.module = module
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
         self.group = group
@@ -94,8 +107,9 @@ class DistributedData:
         self._pending = [0] * len(self._buckets)
         self._reqs = [None] * len(self._buckets)
         self._flat = [None] * len(self._buckets)
-        # compressed: one request over the bucket's gradient list per f32/bf16
-        # bucket; None marks a bucket on the exact path
+        # one request over the bucket's gradient list: compressed for f32/bf16
+        # buckets, exact with grads="in_place" for what is left of f32/bf16/f16;
+        # None marks a bucket on the cat path
         self._seg = [None] * len(self._buckets)
         if compression is not None and self.world > 1:
             for bi, ps in enumerate(self._buckets):
@@ -104,6 +118,13 @@ class DistributedData:
                         self.dist, [q.numel() for q in ps], dtype=_dt(ps[0]),
                         group=group, ar_algo=ar_algo, compression=compression,
                         post_scale=1.0 / self.world if average else 1.0)
+        if grads == "in_place" and self.world > 1:
+            for bi, ps in enumerate(self._buckets):
+                if self._seg[bi] is None and ps[0].dtype in (torch.float32, torch.bfloat16,
+                                                             torch.float16):
+                    self._seg[bi] = mx.SegmentedAllReduce(
+                        self.dist, [q.numel() for q in ps], dtype=_dt(ps[0]), group=group,
+                        compression=None, post_scale=1.0 / self.world if average else 1.0)
 
         for p in self._params:
             p.register_post_accumulate_grad_hook(self._hook)
@@ -125,7 +146,7 @@ class DistributedData:
                 for q, g in zip(ps, grads):
                     if not g.is_contiguous():
                         raise ValueError(
-                            f"compression={self.compression!r} reduces gradients in place "
+                            f"{self._in_place_why()} reduces gradients in place "
                             f"and needs them contiguous: the gradient of a parameter of shape "
                             f"{tuple(q.shape)} has strides {g.stride()}")
                 self._seg[bi].start(grads)
@@ -136,6 +157,10 @@ class DistributedData:
             self._reqs[bi] = self.dist.all_reduce(flat, flat, flat.numel(),
                                                   op="sum", dtype=_dt(p),
                                                   group=self.group)
+
+    def _in_place_why(self):
+        return f"compression={self.compression!r}" if self.compression is not None \
+            else "grads='in_place'"
 
     def finish_gradients(self):
         """Wait all bucket allreduces and scatter averaged grads back."""
@@ -163,7 +188,8 @@ class DistributedData:
         self._reset_counts()
 
     def close(self):
-        """Destroy the compressed buckets' requests (none in flight)."""
+        """Destroy the buckets' list requests, compressed or exact (none in
+        flight)."""
         for bi, r in enumerate(self._seg):
             if r is not None:
                 r.destroy()
