@@ -32,9 +32,15 @@ quant_sum_requant_n at 4 wires) at --melems Mi elements and at 64 Ki elements,
 f32 and bf16, interleaved rounds; and the f32 quantize4/dequantize4 generic
 against fast kernels from 256 KiB to 16 MiB, which is what the launcher's threshold
 is chosen from.
+--mode dequant_segments4_ab: single-GPU A/B of the 4-bit all-gather's finish,
+dequantize_segments4 against the int8 dequantize_segments on the same sizes
+(--melems Mi elements in all, 2 and 8 segments, f32 and bf16, assign and
+accumulate), with the int8 kernel's spread and HIT or MISS per row.
 --bits4, in the allreduce and reduce_scatter modes: the two-shot or direct
-request also runs with bits=4 (up to 8 ranks), next to its int8 self. --kbytes
-sizes the reduce_scatter's send buffer too, instead of --melems."""
+request also runs with bits=4 (up to 8 ranks), next to its int8 self; in the
+all_gather mode the accumulating request does. --kbytes sizes the
+reduce_scatter's send buffer and the all_gather's total too, instead of
+--melems."""
 import argparse
 import json
 import os
@@ -436,11 +442,93 @@ def dequant_segments_ab(args):
         del wire
 
 
+def dequant_segments4_ab(args):
+    """One line of JSON per (nseg, dtype, mode): dequantize_segments4 against
+    the int8 dequantize_segments on the same sizes, --melems Mi elements in
+    all, 2 and 8 segments, block 256, both on the launcher's own path (the
+    fast kernels). Timing as in sum_dequant_ab, rounds interleaved in one
+    process. The goal is int4 <= int8; the margin is the int8 kernel's own
+    spread over the rounds, (max - min) / median: HIT when the int4 median is
+    at most the int8 median times (1 + spread)."""
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("dequant_segments4_ab measures GPU kernels: no GPU found")
+    from mlsl_amd import ops
+    torch.cuda.set_device(0)
+    total, block = args.melems << 20, 256
+    torch.manual_seed(0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters
+
+    for nseg in (2, 8):
+        count = total // nseg
+        assert count % block == 0
+        sw8, sw4 = ops.wire_bytes(count, block), ops.wire_bytes(count, block, 4)
+        wire8 = torch.empty(nseg * sw8, dtype=torch.uint8, device="cuda")
+        wire4 = torch.empty(nseg * sw4, dtype=torch.uint8, device="cuda")
+        for j in range(nseg):
+            v = torch.randn(count, dtype=torch.float32, device="cuda") * (1.0 + j)
+            ops.quantize(v, wire8[j * sw8:(j + 1) * sw8], count, block=block, dtype="f32")
+            ops.quantize4(v, wire4[j * sw4:(j + 1) * sw4], count, block=block, dtype="f32")
+            del v
+        for dtype, tdt, es in (("f32", torch.float32, 4), ("bf16", torch.bfloat16, 2)):
+            out = torch.zeros(total, dtype=tdt, device="cuda")
+            # the same bits as the flat int4 kernel before anything is timed
+            ref = torch.empty_like(out)
+            ops.dequantize4(wire4, ref, total, block=block, dtype=dtype)
+            ops.dequantize_segments4(wire4, out, count, nseg, block=block, dtype=dtype)
+            assert torch.equal(out.view(torch.uint8), ref.view(torch.uint8))
+            del ref
+            for acc in (False, True):
+                variants = {
+                    "int8": lambda: ops.dequantize_segments(
+                        wire8, out, count, nseg, block=block, dtype=dtype, accumulate=acc),
+                    "int4": lambda: ops.dequantize_segments4(
+                        wire4, out, count, nseg, block=block, dtype=dtype, accumulate=acc),
+                }
+                for fn in variants.values():
+                    for _ in range(args.warmup):
+                        fn()
+                times = {k: [] for k in variants}
+                for _ in range(args.rounds):
+                    for k, fn in variants.items():
+                        out.zero_()    # accumulating must not run off to inf
+                        times[k].append(timed(fn))
+                res = {"config": "dequant-segments4-ab", "nseg": nseg, "dtype": dtype,
+                       "mode": "accumulate" if acc else "assign", "melems": args.melems,
+                       "block": block, "iters": args.iters, "rounds": args.rounds}
+                for k, v in times.items():
+                    res[f"{k}_us_median"] = round(_median(v) * 1e6, 1)
+                    res[f"{k}_us_min"] = round(min(v) * 1e6, 1)
+                    res[f"{k}_us_max"] = round(max(v) * 1e6, 1)
+                    wbytes = nseg * (sw8 if k == "int8" else sw4)
+                    nbytes = wbytes + (2 if acc else 1) * total * es
+                    res[f"{k}_min_bytes_per_elem"] = round(nbytes / total, 3)
+                    res[f"{k}_GBps"] = round(nbytes / _median(v) / 1e9, 1)
+                m8, m4 = _median(times["int8"]), _median(times["int4"])
+                spread = (max(times["int8"]) - min(times["int8"])) / m8
+                res["int8_spread"] = round(spread, 3)
+                res["int4_over_int8"] = round(m4 / m8, 3)
+                res["verdict"] = "HIT" if m4 <= m8 * (1 + spread) else "MISS"
+                print(json.dumps(res), flush=True)
+            del out
+        del wire8, wire4
+
+
 def all_gather_bench(args):
     """Quantized all-gather, assign and accumulate, against the exact
-    all-gather of the same elements: --melems elements in all, 1/world of
-    them from each rank (launch with benchmarks/mp_run.py for N>1).
-    --exact-only times the exact request alone."""
+    all-gather of the same elements: --melems elements in all, or --kbytes KiB
+    in all when given, 1/world of them from each rank (launch with
+    benchmarks/mp_run.py for N>1). --exact-only times the exact request alone.
+    --bits4 adds the accumulating request at bits=4 next to its int8 self.
+    Every request is timed --rounds times, the rounds interleaved; ms is the
+    median round and ms_min / ms_max the spread."""
     import torch
     if not torch.cuda.is_available():
         sys.exit("all_gather mode measures the device transport: no GPU found")
@@ -450,7 +538,8 @@ def all_gather_bench(args):
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)) % torch.cuda.device_count())
     es = 2 if args.dtype == "bf16" else 4
     tdt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    count = (args.melems << 20) // size // 256 * 256
+    total = args.kbytes * 1024 // es if args.kbytes else args.melems << 20
+    count = total // size // 256 * 256
     torch.manual_seed(1 + rank)
     send = (torch.randn(count, dtype=torch.float32, device="cuda") * 0.01).to(tdt)
     d = mx.Distribution(size, 1)
@@ -463,34 +552,54 @@ def all_gather_bench(args):
                  ("int8_accumulate", mx.PersistentRequest(
                       d, "all_gather", count, dtype=args.dtype, group="data",
                       quantized=True, accumulate=True))]
-    results, outs = {}, {}
+        if args.bits4:
+            reqs.append(("int4_accumulate", mx.PersistentRequest(
+                d, "all_gather", count, dtype=args.dtype, group="data", quantized=True,
+                accumulate=True, bits=4)))
+    outs = {name: torch.zeros(size * count, dtype=tdt, device="cuda") for name, _ in reqs}
+
+    def run(name, req):
+        req.start(send, outs[name])
+        req.wait()
+
     for name, req in reqs:
-        recv = torch.zeros(size * count, dtype=tdt, device="cuda")
-
-        def run():
-            req.start(send, recv)
-            req.wait()
-
         for _ in range(args.warmup):
-            run()
-        recv.zero_()
-        torch.cuda.synchronize()
-        d.barrier("global")
-        t0 = time.perf_counter()
-        for _ in range(args.iters):
-            run()
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / args.iters
-        results[name] = {"ms": round(dt * 1e3, 3),
-                         "algbw_GBps": round(size * count * es / dt / 1e9, 2)}
-        outs[name] = recv
+            run(name, req)
+    times = {name: [] for name, _ in reqs}
+    for _ in range(args.rounds):
+        for name, req in reqs:
+            outs[name].zero_()
+            torch.cuda.synchronize()
+            d.barrier("global")
+            t0 = time.perf_counter()
+            for _ in range(args.iters):
+                run(name, req)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / args.iters)
+    # one start's result, for the error figures below
+    for name, req in reqs:
+        outs[name].zero_()
+        run(name, req)
+    torch.cuda.synchronize()
+    results = {k: {"ms": round(_median(v) * 1e3, 4), "ms_min": round(min(v) * 1e3, 4),
+                   "ms_max": round(max(v) * 1e3, 4),
+                   "algbw_GBps": round(size * count * es / _median(v) / 1e9, 2)}
+               for k, v in times.items()}
     res = {"config": "int8-quantized-all-gather", "dtype": args.dtype,
-           "total_mib": size * count * es >> 20, "world": size,
+           "total_mib": size * count * es >> 20, "total_bytes": size * count * es,
+           "world": size, "iters": args.iters, "rounds": args.rounds,
            **{f"{k}_{kk}": vv for k, v in results.items() for kk, vv in v.items()}}
     if not args.exact_only:
         x = outs["exact"].float()
         res["assign_max_abs_err"] = round((outs["int8_assign"].float() - x).abs().max().item(), 8)
         res["half_step"] = round(x.abs().max().item() / 254.0, 8)
+    if "int4_accumulate" in times:
+        m8, m4 = _median(times["int8_accumulate"]), _median(times["int4_accumulate"])
+        spread = (max(times["int8_accumulate"]) - min(times["int8_accumulate"])) / m8
+        res["int8_accumulate_spread"] = round(spread, 3)
+        res["int4_over_int8_accumulate"] = round(m4 / m8, 3)
+        res["int4_max_abs_err"] = round((outs["int4_accumulate"].float() - x).abs().max().item(), 8)
+        res["int4_half_step"] = round(x.abs().max().item() / 14.0, 8)
     if rank == 0:
         print(json.dumps(res), flush=True)
     for _, req in reqs:
@@ -503,7 +612,7 @@ def main():
     ap.add_argument("--mode", default="allreduce",
                     choices=["allreduce", "reduce_scatter", "all_gather", "sum_dequant_ab",
                              "sum_dequant_n_ab", "dequant_segments_ab", "sum_requant_n",
-                             "int4_kernels"])
+                             "int4_kernels", "dequant_segments4_ab"])
     ap.add_argument("--exact-only", action="store_true",
                     help="all_gather mode: time the exact request alone")
     ap.add_argument("--melems", type=int, default=64,
@@ -512,9 +621,10 @@ def main():
     ap.add_argument("--mbytes", type=int, default=256)
     ap.add_argument("--kbytes", type=int, default=0,
                     help="message size in KiB instead of --mbytes (allreduce) or --melems "
-                         "(reduce_scatter)")
+                         "(reduce_scatter, all_gather)")
     ap.add_argument("--bits4", action="store_true",
-                    help="allreduce and reduce_scatter modes: also time the bits=4 request")
+                    help="allreduce, reduce_scatter and all_gather modes: also time the "
+                         "bits=4 request")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -530,6 +640,8 @@ def main():
         return sum_requant_n(args)
     if args.mode == "int4_kernels":
         return int4_kernels(args)
+    if args.mode == "dequant_segments4_ab":
+        return dequant_segments4_ab(args)
     if args.mode == "all_gather":
         return all_gather_bench(args)
     rs = args.mode == "reduce_scatter"

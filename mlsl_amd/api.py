@@ -389,12 +389,16 @@ class PersistentRequest:
         """bits: the payload bits per element of a quantized request's wire.
         8 is the int8 wire. 4 is the int4 wire (a block of `set_quant_params`
         elements, a multiple of 8, takes block/2 + 8 bytes where int8 takes
-        block + 8), for kind="all_reduce" and kind="reduce_scatter" only: a
-        request that names no algorithm then runs two_shot or direct,
-        whatever MLSL_QUANT_AR_ALGO and MLSL_QUANT_RS_ALGO say (those choose
-        between int8 algorithms), and naming "ring" is refused, as are more
-        than 8 ranks and a compression plugin. See
-        mlsl_persistent_all_reduce_quantized_bits.
+        block + 8), for kind="all_reduce" and kind="reduce_scatter", and for
+        kind="all_gather" with accumulate=True. A sum that names no
+        algorithm then runs two_shot or direct, whatever MLSL_QUANT_AR_ALGO
+        and MLSL_QUANT_RS_ALGO say (those choose between int8 algorithms),
+        and naming "ring" is refused, as are more than 8 ranks and a
+        compression plugin. See mlsl_persistent_all_reduce_quantized_bits.
+        The 4-bit all_gather accumulates only (an assigned value would keep
+        15 levels per block; accumulated differences correct themselves from
+        start to start) and has no rank limit. See
+        mlsl_persistent_all_gather_quantized_bits.
         algo: quantized reduce_scatter only. None takes MLSL_QUANT_RS_ALGO
         (ring unless set); "ring" or "direct" names it. See
         mlsl_persistent_reduce_scatter_quantized_algo.
@@ -418,10 +422,13 @@ class PersistentRequest:
         if bits != 8 and not quantized:
             raise ValueError("bits= names the quantized wire's payload: it needs "
                              "quantized=True")
-        if bits == 4 and kind not in ("all_reduce", "reduce_scatter"):
+        if bits == 4 and not (kind in ("all_reduce", "reduce_scatter") or
+                              (kind == "all_gather" and accumulate)):
             raise ValueError(f'bits=4 is not wired to kind="{kind}": the 4-bit wire codec '
-                             'serves kind="all_reduce" (two_shot) and '
-                             'kind="reduce_scatter" (direct) only')
+                             'serves kind="all_reduce" (two_shot), '
+                             'kind="reduce_scatter" (direct) and kind="all_gather" with '
+                             'accumulate=True only (an assigning 4-bit all_gather would '
+                             'leave a gathered value 15 levels per block)')
         if quantized and kind == "all_to_all":
             raise ValueError('quantized=True is not supported for kind="all_to_all"')
         if algo is not None:
@@ -462,6 +469,9 @@ class PersistentRequest:
                                                      P(c_void_p)]
             L.mlsl_persistent_all_gather_quantized.argtypes = [
                 c_void_p, c_size_t, c_int, c_int, c_int, P(c_void_p)]
+            L.mlsl_persistent_all_gather_quantized_bits.argtypes = [
+                c_void_p, c_size_t, c_int, c_int, c_int, c_int, P(c_void_p)]
+            L.mlsl_persistent_all_gather_quantized_bits.restype = c_int
             L.mlsl_persistent_all_to_all.argtypes = [c_void_p, c_size_t, c_int, c_int,
                                                      P(c_void_p)]
             L.mlsl_request_start.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -477,7 +487,11 @@ class PersistentRequest:
                 getattr(L, n).restype = c_int
             L._persist_declared = True
         h = c_void_p()
-        if bits == 4:
+        if bits == 4 and kind == "all_gather":
+            # the int4 wire, accumulating finish only (checked above)
+            check(L.mlsl_persistent_all_gather_quantized_bits(
+                dist._h, count, DTYPE[dtype], GROUP[group], 1, bits, ctypes.byref(h)))
+        elif bits == 4:
             # the int4 wire: two_shot / direct unless named; "ring" raises
             named, table, fn = ((ar_algo, QUANT_AR_ALGO,
                                  L.mlsl_persistent_all_reduce_quantized_bits)

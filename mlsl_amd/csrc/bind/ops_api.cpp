@@ -221,6 +221,22 @@ int mlsl_hip_dequantize_segments(const void* wire, size_t nseg, void* out, size_
     OPS_CATCH
 }
 
+int mlsl_hip_dequantize_segments4(const void* wire, size_t nseg, void* out, size_t count,
+                                  size_t block, int dt, int accumulate, int path) {
+    OPS_TRY LaunchDequantizeSegments4(wire, nseg, out, count, block,
+                                      static_cast<DataType>(dt), accumulate != 0, nullptr,
+                                      static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_host_dequantize_segments4(const void* wire, size_t nseg, void* out, size_t count,
+                                   size_t block, int dt, int accumulate) {
+    OPS_TRY HostDequantizeSegments(wire, nseg, out, count, block,
+                                   static_cast<DataType>(dt), accumulate != 0, 4);
+    OPS_CATCH
+}
+
 }  // extern "C"
 
 namespace {

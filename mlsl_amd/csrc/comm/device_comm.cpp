@@ -683,7 +683,8 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
                                  p.residual, s);
     } else {
         // p.bits == 4: the int4 codec (two-shot allreduce, flat or over a list,
-        // and flat direct reduce-scatter only; Setup() refused everything else)
+        // flat direct reduce-scatter and accumulating all-gather only; Setup()
+        // refused everything else)
         for (size_t j = 0; j < p.nseg; ++j) {
             const uint8_t* in = sbuf + j * p.seg_bytes;
             uint8_t* err = p.residual ? base + p.err_off + j * p.seg_bytes : nullptr;
@@ -719,8 +720,12 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
                 LaunchDequantize(wires[0], rbuf, p.count, p.block, dt, s);
             break;
         case QuantFinish::SCATTER:
-            LaunchDequantizeSegments(wires[0], p.out_segs, rbuf, p.count, p.block, dt,
-                                     p.accumulate, s);
+            if (p.bits == 4)
+                LaunchDequantizeSegments4(wires[0], p.out_segs, rbuf, p.count, p.block, dt,
+                                          p.accumulate, s);
+            else
+                LaunchDequantizeSegments(wires[0], p.out_segs, rbuf, p.count, p.block, dt,
+                                         p.accumulate, s);
             break;
     }
 }

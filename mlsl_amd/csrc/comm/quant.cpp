@@ -266,13 +266,13 @@ void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
 }
 
 void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t count,
-                            size_t block, DataType dt, bool accumulate) {
-    CheckQuantBlock(block, "HostDequantizeSegments");
+                            size_t block, DataType dt, bool accumulate, int bits) {
+    CheckQuantBlock(block, "HostDequantizeSegments", bits);
     if (dt != DataType::F32 && dt != DataType::BF16)
         MLSL_THROW("segmented dequantize supports f32/bf16 only");
     MLSL_CHECK(nseg >= 1, "segmented dequantize takes at least one segment");
     const size_t nblocks = (count + block - 1) / block;
-    const size_t seg_wire = nblocks * (block + 8);
+    const size_t seg_wire = nblocks * WireBlock(block, bits);
     for (size_t seg = 0; seg < nseg; ++seg) {
         // every segment has a block grid of its own: a partial last block is
         // followed by the next segment's block 0, not by the rest of a block
@@ -280,12 +280,12 @@ void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t cou
         for (size_t blk = 0; blk < nblocks; ++blk) {
             const size_t base = seg * count + blk * block;
             const size_t n = std::min(block, count - blk * block);
-            const uint8_t* wb = w + blk * (block + 8);
+            const uint8_t* wb = w + blk * WireBlock(block, bits);
             float s;
             std::memcpy(&s, wb, 4);
-            const int8_t* p = reinterpret_cast<const int8_t*>(wb + 8);
+            const uint8_t* p = wb + kWireHdr;
             for (size_t i = 0; i < n; ++i) {
-                const float q = static_cast<float>(p[i]);
+                const float q = static_cast<float>(PayloadGet(p, i, bits));
                 if (dt == DataType::F32) {
                     float* o = static_cast<float*>(out) + base + i;
                     *o = accumulate ? std::fmaf(q, s, *o) : q * s;

@@ -55,9 +55,11 @@ void HostQuantSumRequantN(const void* const* wires, int nwires, void* dst_wire,
 // own, and segment j goes to out[j * count, (j + 1) * count): assigned as
 // HostDequantize does it, or with `accumulate` as out = fmaf(q, scale, out)
 // in float, rounded once into the element type. Any nseg >= 1; the wire is
-// not written. Bit for bit what LaunchDequantizeSegments computes.
+// not written. Bit for bit what LaunchDequantizeSegments computes, and at
+// bits = 4 (segment wires of QuantWireBytes(count, block, 4) bytes) what
+// LaunchDequantizeSegments4 does.
 void HostDequantizeSegments(const void* wire, size_t nseg, void* out, size_t count,
-                            size_t block, DataType dt, bool accumulate);
+                            size_t block, DataType dt, bool accumulate, int bits = 8);
 
 // Prologue and finish of the quantized allreduce over a list of tensors, whose
 // concatenation V (count elements) is never materialised: tensor j holds

@@ -277,14 +277,22 @@ void CommRequest::BuildChunks() {
             MLSL_CHECK(plugin_ == nullptr,
                        "the 4-bit wire codec cannot run with a compression plugin (the "
                        "plugin declares its own wire block); unset lib_path or use bits=8");
-            MLSL_CHECK(spec_.op != CollOp::ALLGATHER && spec_.op != CollOp::ALLGATHERV,
-                       "the 4-bit wire codec is not wired to all_gather; use bits=8");
+            MLSL_CHECK(spec_.op != CollOp::ALLGATHERV,
+                       "the 4-bit wire codec is not wired to all_gatherv; use all_gather "
+                       "with accumulate");
+            // Assigning would cap every gathered value at 15 levels per block.
+            // Accumulating a difference corrects itself: what one start's
+            // quantization drops is still in the difference at the next.
+            MLSL_CHECK(spec_.op != CollOp::ALLGATHER || qag_accumulate_,
+                       "the 4-bit wire codec is not wired to the assigning all_gather (15 "
+                       "levels per block would be all a gathered value keeps); the 4-bit "
+                       "all_gather exists with accumulate only; use bits=8");
             MLSL_CHECK(!SegmentedReduceScatter(),
                        "the 4-bit wire codec is not wired to the reduce_scatter over a tensor "
                        "list (the all_reduce over a tensor list is); use bits=8");
             MLSL_CHECK(Compressed(),
-                       "the 4-bit wire codec serves all_reduce and reduce_scatter sums of "
-                       "f32/bf16 only");
+                       "the 4-bit wire codec serves all_reduce and reduce_scatter sums and "
+                       "the accumulating all_gather, of f32/bf16 only");
         }
         // an all-gather that was asked to be quantized is never run exact
         // behind the caller's back
@@ -963,7 +971,8 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                                 break;
                             case QuantFinish::SCATTER:
                                 HostDequantizeSegments(wires[0], qp.out_segs, rbase, qp.count,
-                                                       qp.block, dtype_, qp.accumulate);
+                                                       qp.block, dtype_, qp.accumulate,
+                                                       qp.bits);
                                 break;
                         }
                     }

@@ -2743,6 +2743,173 @@ void LaunchDequantizeScatter4(const void* wire, void* const* seg_ptrs,
 }
 
 // ---------------------------------------------------------------------------
+// Segmented dequantize on the int4 wire: the finish of the 4-bit all-gather.
+// LaunchDequantizeSegments' problem (nseg segment wires back to back, every one
+// on a block grid of its own, segment j to out[j * count, (j + 1) * count), one
+// launch, wire block `idx` at idx * (block / 2 + 8) whatever its segment) with
+// the int4 section's ownership rule: a lane owns whole payload words, eight
+// consecutive elements each.
+//
+// Minimum traffic per element: half a wire byte (+ 8 per block) in, sizeof(T)
+// out, and with ACC another sizeof(T) in. f32: 4.53 B assign, 8.53 B
+// accumulate; bf16: 2.53 B and 4.53 B (block 256).
+//
+// Compiled without packed fp32 instructions like the int4 sections above, and
+// for their reason: pinned bit for bit to the host twin.
+
+namespace {
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+
+// Generic path: any legal block, partial last blocks and words, any alignment.
+// One wave per wire block; lanes own words lane, lane + 64, ...
+template <typename T, bool ACC>
+__global__ void DequantizeSegments4Kernel(const uint8_t* __restrict__ wire, T* out,
+                                          size_t count, size_t block_elems,
+                                          uint32_t nblocks, FastDiv by_nblocks,
+                                          uint32_t total) {
+    ForEachWaveBlock(total, [&](size_t vidx, int lane) {
+        // uniform across the wave: segment, block and both addresses stay in
+        // scalar registers (as in DequantizeSegmentsKernel)
+        const uint32_t idx = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vidx));
+        const uint32_t seg = FDiv(idx, by_nblocks);
+        const uint32_t blk = idx - seg * nblocks;
+        const size_t base = static_cast<size_t>(blk) * block_elems;
+        const size_t n = min(block_elems, count - base);
+        const uint8_t* wblock = wire + static_cast<size_t>(idx) * Wire4BlockBytes(block_elems);
+        const float scale = WireScale(wblock);
+        const uint32_t* payload = reinterpret_cast<const uint32_t*>(wblock + kWireHdr);
+        // Segment j starts j * count elements in: with an odd count an aligned
+        // `out` has misaligned segments, so a lane decides per word.
+        T* o = out + static_cast<size_t>(seg) * count + base;
+        for (size_t w = lane; w * 8 < n; w += 64) {
+            const uint32_t packed = payload[w];
+            T* p = o + w * 8;
+            if (w * 8 + 8 <= n && Aligned16(p)) {
+                if constexpr (sizeof(T) == 4) {
+                    float4_ev v0{}, v1{};
+                    if constexpr (ACC) {
+                        v0 = *reinterpret_cast<const float4_ev*>(p);
+                        v1 = *reinterpret_cast<const float4_ev*>(p + 4);
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        v0[j] = DequantElem<T, ACC>(QUnpack4(packed, j), scale, v0[j]);
+                        v1[j] = DequantElem<T, ACC>(QUnpack4(packed, 4 + j), scale, v1[j]);
+                    }
+                    StoreVec<false>(v0, p);
+                    StoreVec<false>(v1, p + 4);
+                } else {
+                    ushort8_t v{};
+                    if constexpr (ACC) v = *reinterpret_cast<const ushort8_t*>(p);
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        v[j] = DequantElem<T, ACC>(QUnpack4(packed, j), scale, v[j]);
+                    StoreVec<false>(v, p);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    if (w * 8 + j < n)
+                        p[j] = DequantElem<T, ACC>(QUnpack4(packed, j), scale, ACC ? p[j] : T{});
+            }
+        }
+    });
+}
+
+// Fast path (block 256, whole blocks, 16-B aligned `out`, 8-B aligned wire):
+// every segment is whole blocks, so wire and output are both flat runs of
+// `nblocks` blocks in all. One block per half-wave. bf16: lane `sub` owns word
+// `sub`, one 4-B load and one 16-B load/store of `out`. f32 takes
+// Dequantize4X2Kernel's split-half layout, for its recorded reason: lane `sub`
+// handles elements [4 sub, +4) and [128 + 4 sub, +4) from the low or high half
+// of words sub >> 1 and 16 + (sub >> 1), every 16-B access contiguous across
+// the half-wave; with ACC the loads of `out` follow the stores' layout.
+template <typename T, bool ACC, bool NT_ST>
+__global__ void DequantizeSegments4X2Kernel(const uint8_t* __restrict__ wire, T* out,
+                                            size_t nblocks) {
+    ForEachHalfWaveBlock(nblocks, [&](size_t blk, int sub) {
+        const uint8_t* wblock = wire + blk * kFast4Bytes;
+        const float scale = WireScale(wblock);
+        const uint32_t* payload = reinterpret_cast<const uint32_t*>(wblock + kWireHdr);
+        T* obase = out + blk * kFastBlock;
+        if constexpr (sizeof(T) == 4) {
+            const int shift = (sub & 1) * 16;
+            const uint32_t p0 = payload[sub >> 1] >> shift;
+            const uint32_t p1 = payload[16 + (sub >> 1)] >> shift;
+            float4_ev o0{}, o1{};
+            if constexpr (ACC) {
+                o0 = *reinterpret_cast<const float4_ev*>(obase + sub * 4);
+                o1 = *reinterpret_cast<const float4_ev*>(obase + 128 + sub * 4);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o0[j] = DequantElem<T, ACC>(QUnpack4(p0, j), scale, o0[j]);
+                o1[j] = DequantElem<T, ACC>(QUnpack4(p1, j), scale, o1[j]);
+            }
+            StoreVec<NT_ST>(o0, obase + sub * 4);
+            StoreVec<NT_ST>(o1, obase + 128 + sub * 4);
+        } else {
+            const uint32_t packed = payload[sub];
+            ushort8_t v{};
+            if constexpr (ACC) v = *reinterpret_cast<const ushort8_t*>(obase + sub * 8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                v[j] = DequantElem<T, ACC>(QUnpack4(packed, j), scale, v[j]);
+            StoreVec<NT_ST>(v, obase + sub * 8);
+        }
+    });
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
+}  // namespace
+
+void LaunchDequantizeSegments4(const void* wire, size_t nseg, void* out, size_t count,
+                               size_t block_elems, DataType dt, bool accumulate,
+                               hipStream_t stream, Quant4Path path) {
+    CheckQuantBlock(block_elems, "LaunchDequantizeSegments4", 4);
+    CheckQuant4Dtype(dt, "int4 segmented dequantize");
+    MLSL_CHECK(nseg >= 1, "int4 segmented dequantize takes at least one segment");
+    MLSL_CHECK((reinterpret_cast<uintptr_t>(wire) & 3) == 0,
+               "int4 segmented dequantize: the wire must be 4-byte aligned");
+    if (count == 0) return;
+    const size_t nblocks = NumBlocks(count, block_elems);
+    const size_t total = nseg * nblocks;
+    // AUTO takes the fast path wherever it fits: no size floor
+    const bool fast = TakeFast4(
+        path, Fits4(count, block_elems, out, nullptr, reinterpret_cast<uintptr_t>(wire)), true,
+        "LaunchDequantizeSegments4");
+    MLSL_CHECK(fast || total <= 0xffffffffull,
+               "int4 segmented dequantize: too many wire blocks");
+    const uint8_t* w = static_cast<const uint8_t*>(wire);
+    auto launch = [&](auto* o) {
+        using T = std::remove_pointer_t<decltype(o)>;
+        DispatchBool(accumulate, [&](auto acc) {
+            constexpr bool ACC = decltype(acc)::value;
+            if (fast) {
+                // nontemporal stores under LaunchDequantizeSegments' size rule
+                DispatchBool(nseg * count * sizeof(T) >= kSumDequantNtBytes, [&](auto nt) {
+                    DequantizeSegments4X2Kernel<T, ACC, decltype(nt)::value>
+                        <<<PairGrid(total), dim3(kBlock), 0, stream>>>(w, o, total);
+                });
+            } else {
+                DequantizeSegments4Kernel<T, ACC><<<WaveGrid(total), dim3(kBlock), 0, stream>>>(
+                    w, o, count, block_elems, static_cast<uint32_t>(nblocks),
+                    MakeFastDiv(static_cast<uint32_t>(nblocks)), static_cast<uint32_t>(total));
+            }
+        });
+    };
+    if (dt == DataType::F32) launch(static_cast<float*>(out));
+    else launch(static_cast<unsigned short*>(out));
+    HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------
 // The exact members of the list family: the concatenation V of a list of
 // tensors copied into one flat buffer, and the flat buffer scaled back into
 // the tensors. Same two device tables as above.

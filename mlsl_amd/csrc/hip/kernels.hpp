@@ -197,6 +197,23 @@ void LaunchDequantizeScatter4(const void* wire, void* const* seg_ptrs,
                               size_t block_elems, DataType dt, float post_scale,
                               bool round_first, hipStream_t stream,
                               Quant4Path path = Quant4Path::AUTO);
+// LaunchDequantizeSegments on the int4 wire: the finish of the 4-bit
+// all-gather. `wire` holds nseg segment wires of NumBlocks(count) int4 blocks
+// each, back to back (wire block idx of the launch at idx * (block_elems / 2 +
+// 8)), 4-byte aligned; segment j goes to out[j * count, (j + 1) * count):
+// Encode(q * scale), or with `accumulate` Encode(fma(q, scale, Decode(out))),
+// one explicit fma rounded once into the element type (fp32/bf16). GENERIC is
+// one wave per wire block, a lane deciding per payload word between 16-byte
+// accesses and a guarded element walk, so `out` and count may have any
+// alignment; FAST is one block per half-wave and needs block 256, count a
+// multiple of 256, `out` 16-byte and the wire 8-byte aligned (it throws
+// elsewhere); AUTO takes FAST wherever it fits. Outputs of 128 MiB and more
+// are stored nontemporally on the fast path. The wire is not written and
+// nothing outside out[0, nseg * count) is. Quant4BlocksPerTrip holds. The host
+// twin is HostDequantizeSegments at bits = 4.
+void LaunchDequantizeSegments4(const void* wire, size_t nseg, void* out, size_t count,
+                               size_t block_elems, DataType dt, bool accumulate,
+                               hipStream_t stream, Quant4Path path = Quant4Path::AUTO);
 // The exact pair over the same tables, f32/bf16/f16 (anything else throws
 // "supports f32/bf16/f16 only"). Gather: flat[i] = V[i], the bits unchanged
 // (NaN payloads and -0 survive); the tensors are only read and nothing outside

@@ -131,9 +131,9 @@ int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
  * algorithms), and the ring fails at creation: it requantizes on every hop,
  * which at 4 bits loses far more than at 8. Also failing at creation at 4
  * bits: a group of more than 8 ranks, a compression plugin, a block that is
- * no multiple of 8; and any bits other than 4 or 8. The all-gather and the
- * reduce-scatter over a tensor list have no 4-bit form; the allreduce over a
- * tensor list has one (mlsl_persistent_all_reduce_quantized_segments_bits). */
+ * no multiple of 8; and any bits other than 4 or 8. The reduce-scatter over a
+ * tensor list has no 4-bit form; the allreduce over a tensor list has one
+ * (mlsl_persistent_all_reduce_quantized_segments_bits). */
 int mlsl_persistent_all_reduce_quantized_bits(mlsl_distribution d, size_t count,
                                               mlsl_data_type dt, mlsl_reduction op,
                                               mlsl_group g, int algo, int bits,
@@ -142,6 +142,19 @@ int mlsl_persistent_reduce_scatter_quantized_bits(mlsl_distribution d, size_t re
                                                   mlsl_data_type dt, mlsl_reduction op,
                                                   mlsl_group g, int algo, int bits,
                                                   mlsl_request* out);
+/* mlsl_persistent_all_gather_quantized (below) with the payload bits of its
+ * wire named: bits == 8 is that function. bits == 4 is the int4 wire above,
+ * and exists with accumulate != 0 only: recv[r*send_count + i] =
+ * fma(q_r[i], scale_r, recv[...]) in float, rounded once into dt, q in -7..7.
+ * It is meant for differences (a sharded optimizer's master - replica): what
+ * one start's quantization drops is still in the difference at the next, so
+ * the scheme corrects itself with no residual. accumulate == 0 at 4 bits
+ * fails at creation: an assigned value would keep 15 levels per block. No
+ * rank limit. Also failing at creation: anything but f32/bf16, a compression
+ * plugin, a block that is no multiple of 8, bits other than 4 or 8. */
+int mlsl_persistent_all_gather_quantized_bits(mlsl_distribution d, size_t send_count,
+                                              mlsl_data_type dt, mlsl_group g, int accumulate,
+                                              int bits, mlsl_request* out);
 /* The int8-quantized allreduce (a sum) over a LIST of nseg tensors of
  * counts[j] >= 1 elements each, in place: it is the quantized allreduce of
  * their concatenation, which is never built. The quantize prologue reads the

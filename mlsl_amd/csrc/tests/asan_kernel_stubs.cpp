@@ -107,6 +107,7 @@ void LaunchQuantizeGatherShards(const void* const* ptrs, const uint64_t* offs, s
 void LaunchDequantizeScatter(const void* w, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, size_t blk, DataType dt, float post, bool round_first, hipStream_t st) STUB(LaunchDequantizeScatter, w, ptrs, offs, nseg, n, blk, dt, post, round_first, st)
 void LaunchQuantizeGather4(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st, Quant4Path path) STUB(LaunchQuantizeGather4, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st, path)
 void LaunchDequantizeScatter4(const void* w, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, size_t blk, DataType dt, float post, bool round_first, hipStream_t st, Quant4Path path) STUB(LaunchDequantizeScatter4, w, ptrs, offs, nseg, n, blk, dt, post, round_first, st, path)
+void LaunchDequantizeSegments4(const void* w, size_t nseg, void* out, size_t n, size_t blk, DataType dt, bool acc, hipStream_t st, Quant4Path path) STUB(LaunchDequantizeSegments4, w, nseg, out, n, blk, dt, acc, st, path)
 void LaunchGatherList(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* flat, size_t n, DataType dt, hipStream_t st) STUB(LaunchGatherList, ptrs, offs, nseg, flat, n, dt, st)
 void LaunchScatterScaleList(const void* flat, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, DataType dt, float post, hipStream_t st) STUB(LaunchScatterScaleList, flat, ptrs, offs, nseg, n, dt, post, st)
 void LaunchPack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchPack, s, d, pd, dt, st)

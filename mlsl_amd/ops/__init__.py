@@ -68,6 +68,11 @@ def _lib():
         L.mlsl_host_dequantize_segments.argtypes = L.mlsl_hip_dequantize_segments.argtypes
         L.mlsl_hip_dequantize_segments.restype = c.c_int
         L.mlsl_host_dequantize_segments.restype = c.c_int
+        L.mlsl_hip_dequantize_segments4.argtypes = \
+            L.mlsl_hip_dequantize_segments.argtypes + [c.c_int]
+        L.mlsl_host_dequantize_segments4.argtypes = L.mlsl_hip_dequantize_segments.argtypes
+        L.mlsl_hip_dequantize_segments4.restype = c.c_int
+        L.mlsl_host_dequantize_segments4.restype = c.c_int
         L.mlsl_hip_quantize_gather.argtypes = [c.POINTER(c.c_void_p),
                                                c.POINTER(c.c_size_t), c.c_size_t,
                                                c.c_void_p, c.c_void_p, c.c_size_t,
@@ -359,6 +364,24 @@ def dequantize_segments(wire, out, count, nseg, block=256, dtype=None, accumulat
     dt = dtype or d1
     check(_lib().mlsl_hip_dequantize_segments(wp, nseg, op_, count, block, DTYPE[dt],
                                               1 if accumulate else 0))
+
+
+def dequantize_segments4(wire, out, count, nseg, block=256, dtype=None, accumulate=False,
+                         path=None):
+    """`dequantize_segments` of int4 wires, the finish of the all_gather at
+    bits=4: `wire` holds `nseg` segment wires of wire_bytes(count, block, 4)
+    bytes back to back, 4-byte aligned, and segment j goes to
+    out[j*count:(j+1)*count] (f32/bf16) as q * scale, or with accumulate=True
+    as fma(q, scale, out) in float, rounded once. `out` and count may have any
+    alignment. path as in `quantize4`: "fast" needs block 256, count a multiple
+    of 256, `out` 16-byte and the wire 8-byte aligned; None takes it wherever
+    it fits."""
+    _check_block4(block)
+    wp, _ = _as_ptr_dtype(wire)
+    op_, d1 = _as_ptr_dtype(out)
+    check(_lib().mlsl_hip_dequantize_segments4(wp, nseg, op_, count, block,
+                                               DTYPE[dtype or d1], 1 if accumulate else 0,
+                                               _PATH4[path]))
 
 
 def _seg_tables(tensors, counts, dtype):
@@ -811,6 +834,16 @@ def host_dequantize_segments(wire, out, count, nseg, block=256, dtype="f32",
     op_ = _host_buf(out, nseg * count * _ELEM_BYTES[dtype], "out")
     check(_lib().mlsl_host_dequantize_segments(wp, nseg, op_, count, block, DTYPE[dtype],
                                                1 if accumulate else 0))
+
+
+def host_dequantize_segments4(wire, out, count, nseg, block=256, dtype="f32",
+                              accumulate=False):
+    """Host twin of `dequantize_segments4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    wp = _host_buf(wire, nseg * wire_bytes(count, block, 4), "wire")
+    op_ = _host_buf(out, nseg * count * _ELEM_BYTES.get(dtype, 8), "out")
+    check(_lib().mlsl_host_dequantize_segments4(wp, nseg, op_, count, block, DTYPE[dtype],
+                                                1 if accumulate else 0))
 
 
 def pack(src, dst, *, mb_offset, mb_count, fm_offset, fm_count, fm_size,

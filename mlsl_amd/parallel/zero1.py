@@ -29,7 +29,7 @@ each flat buffer per step (the reference's grad RS + increment AG pair).
 With ``compression="int8"`` that reduce_scatter travels as int8 wire blocks
 with error feedback (one persistent request, so the residual carries over
 from step to step). The parameter all_gather is exact unless
-``ag_compression="int8"`` is given: see the class.
+``ag_compression="int8"`` or ``"int4"`` is given: see the class.
 With ``grads="in_place"`` on top of that the int8 wire is built straight from
 the gradients where they lie (one ``mx.SegmentedReduceScatter`` over
 ``[p.grad ...]``): the flat gradient buffer, as large as the model, and the
@@ -65,8 +65,16 @@ class ShardedOptimizer:
       the next step: the scheme corrects itself, which is why the request
       carries no residual of its own.
 
-    It needs f32 or bf16 parameters, is independent of ``reduce``,
-    ``compression`` and ``rs_algo``, and costs one extra shard (``master``)
+    ``ag_compression="int4"`` is the same scheme on the 4-bit wire (block/2 + 8
+    bytes per block where int8 takes block + 8): ``scale = max|delta| / 7``,
+    so a step drops at most ``max|delta| / 14`` per element of a block. With
+    no new gradient the replica's distance to ``master`` so shrinks by 14x
+    per step where int8's shrinks by 254x, down to the rounding of the
+    replica's own dtype. With ``compression="int4"`` both of a step's
+    exchanges then travel at 4 bits.
+
+    Either needs f32 or bf16 parameters, is independent of ``reduce``,
+    ``compression``, ``rs_algo`` and ``grads``, and costs one extra shard (``master``)
     and one delta shard per rank. A group of one exchanges nothing and steps
     on ``flat`` as without it. A model checkpoint holds replica values; a
     newly constructed optimizer seeds ``master`` from them.
@@ -92,7 +100,10 @@ class ShardedOptimizer:
         at most 8 ranks, N-1 shard-wires of scratch instead of 2).
         ag_compression: "none" (exact parameter all_gather), or "int8": the
         quantized, accumulating all_gather of master - replica described in
-        the class docstring (f32 or bf16 parameters).
+        the class docstring (f32 or bf16 parameters). "int4" is that
+        all_gather on the 4-bit wire, PersistentRequest(..., accumulate=True,
+        bits=4): about half the wire bytes, any number of ranks, the block
+        size a multiple of 8.
         grads: "copy" gathers every gradient into one flat buffer as large as
         the parameters (``flat_grad``) before it is reduced. "in_place" (needs
         reduce="rs" and compression="int8"; any rs_algo and ag_compression)
@@ -132,8 +143,9 @@ class ShardedOptimizer:
             raise ValueError('rs_algo= selects the quantized reduce_scatter\'s '
                              'algorithm: it needs compression="int8"')
         self.rs_algo = rs_algo
-        if ag_compression not in ("none", "int8"):
-            raise ValueError(f"ag_compression={ag_compression!r}: expected 'none' or 'int8'")
+        if ag_compression not in ("none", "int8", "int4"):
+            raise ValueError(f"ag_compression={ag_compression!r}: expected 'none', 'int8' "
+                             "or 'int4'")
         self.ag_compression = ag_compression
         if grads not in ("copy", "in_place"):
             raise ValueError(f"grads={grads!r}: expected 'copy' or 'in_place'")
@@ -154,8 +166,9 @@ class ShardedOptimizer:
         if compression != "none" and dt not in (torch.float32, torch.bfloat16):
             raise ValueError(f'compression="{compression}" supports f32/bf16 parameters, '
                              f'not {dt}')
-        if ag_compression == "int8" and dt not in (torch.float32, torch.bfloat16):
-            raise ValueError(f'ag_compression="int8" supports f32/bf16 parameters, not {dt}')
+        if ag_compression != "none" and dt not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'ag_compression="{ag_compression}" supports f32/bf16 '
+                             f'parameters, not {dt}')
         total = sum(p.numel() for p in self.params)
         # pad so the shard divides evenly (owned = ceil math in the
         # reference, mlsl_impl.cpp:401-411; padding is the flat analog)
@@ -176,15 +189,16 @@ class ShardedOptimizer:
         self.own_param = self.flat[lo:lo + self.shard]
         self.own_grad = (torch.zeros(self.shard, dtype=dt, device=dev) if self._in_place
                          else self.flat_grad[lo:lo + self.shard])
-        # int8 all_gather: the optimizer steps on an exact copy of the shard
-        # and flat is the replica everywhere; built once, like _qrs
+        # quantized all_gather: the optimizer steps on an exact copy of the
+        # shard and flat is the replica everywhere; built once, like _qrs
         self.master = self._delta = self._qag = None
-        if ag_compression == "int8" and self.world > 1:
+        if ag_compression != "none" and self.world > 1:
             self.master = self.own_param.detach().clone()
             self._delta = torch.zeros_like(self.master)
             self._qag = mx.PersistentRequest(self.dist, "all_gather", self.shard,
                                              dtype=_dt(self.flat), group=group,
-                                             quantized=True, accumulate=True)
+                                             quantized=True, accumulate=True,
+                                             bits=4 if ag_compression == "int4" else 8)
         # the wrapped optimizer sees ONLY the owned shard (state: 1/dp)
         shard_param = torch.nn.Parameter(
             self.own_param if self.master is None else self.master, requires_grad=False)
@@ -270,7 +284,7 @@ class ShardedOptimizer:
         self._shard_holder.grad = None
 
         if self._qag is not None:
-            # what the replica lacks, last step's rounding included, as int8;
+            # what the replica lacks, last step's rounding included, quantized;
             # every rank adds every segment the same way
             torch.sub(self.master, self.own_param, out=self._delta)
             self._qag.start(self._delta, self.flat)
