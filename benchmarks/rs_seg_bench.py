@@ -26,6 +26,12 @@ is one SegmentedReduceScatter over the tensors into a shard-sized tensor.
 Device events on the compute stream bracket each whole sequence (the request
 is waited for before the closing event is recorded), a barrier before each.
 
+--bits4 measures the int4 wire instead: `shards` is quantize_gather_shards4,
+`flat` the flat quantize4, the requests SegmentedReduceScatter(compression=
+"int4") and the flat bits=4 request (both direct). Kernels mode then adds
+`int8_<layout>`, the int8 quantize_gather_shards launch on the same tensors in
+the same process, and reports shards over it.
+
 One JSON line per configuration. No GPU: exits with an error."""
 import argparse
 import json
@@ -71,13 +77,19 @@ def kernels(args):
 
     for nshards in (2, 4):
         shard = total // nshards
-        stride = ops.wire_bytes(shard, block)
+        bits = 4 if args.bits4 else 8
+        stride = ops.wire_bytes(shard, block, bits)
+        wire8 = torch.empty(nshards * ops.wire_bytes(shard, block) if args.bits4 else 0,
+                            dtype=torch.uint8, device="cuda")
         wire = torch.empty(nshards * stride, dtype=torch.uint8, device="cuda")
 
         assert shard % block == 0   # so that one flat launch writes the N shards' bytes
 
         def flat_quantize(wire=wire):
-            ops.quantize(src, wire, total, err=err, block=block, dtype=args.dtype)
+            if args.bits4:
+                ops.quantize4(src, wire, total, err=err, block=block, dtype=args.dtype)
+            else:
+                ops.quantize(src, wire, total, err=err, block=block, dtype=args.dtype)
 
         variants = {"flat_a": flat_quantize, "flat_b": flat_quantize}
         err_diff = {}
@@ -90,9 +102,14 @@ def kernels(args):
 
             def shards(d_ptrs=d_ptrs, d_offs=d_offs, n=len(counts), wire=wire, shard=shard,
                        stride=stride, nshards=nshards):
-                ops.quantize_gather_shards_tables(d_ptrs, d_offs, n, total, wire, nshards, shard,
-                                                  err=err, block=block, dtype=args.dtype,
-                                                  wire_stride=stride)
+                f = ops.quantize_gather_shards4_tables if args.bits4 \
+                    else ops.quantize_gather_shards_tables
+                f(d_ptrs, d_offs, n, total, wire, nshards, shard, err=err, block=block,
+                  dtype=args.dtype, wire_stride=stride)
+
+            def int8(d_ptrs=d_ptrs, d_offs=d_offs, n=len(counts), shard=shard, nshards=nshards):
+                ops.quantize_gather_shards_tables(d_ptrs, d_offs, n, total, wire8, nshards,
+                                                  shard, err=err, block=block, dtype=args.dtype)
 
             def copy(views=views, offs=offs):
                 for v, a, b in zip(views, offs[:-1], offs[1:]):
@@ -111,6 +128,8 @@ def kernels(args):
             err_diff[name] = int((err != e_ref).sum())
             variants[f"shards_{name}"] = shards
             variants[f"copy_{name}"] = copy
+            if args.bits4:
+                variants[f"int8_{name}"] = int8
 
         def timed(fn):
             us = 0.0
@@ -134,7 +153,7 @@ def kernels(args):
                 times[k].append(timed(fn))
         med = {k: _stats(v)["median"] for k, v in times.items()}
         fl = min(med["flat_a"], med["flat_b"])
-        res = {"config": "quant-rs-seg-kernels", "dtype": args.dtype,
+        res = {"config": "quant-rs-seg-kernels", "bits": bits, "dtype": args.dtype,
                "total_mib": total * es >> 20, "nshards": nshards, "block": block,
                "iters": args.iters, "rounds": args.rounds,
                **{f"{k}_us": _stats(v) for k, v in times.items()},
@@ -144,6 +163,9 @@ def kernels(args):
             res[f"shards_{name}_over_flat"] = round(med[f"shards_{name}"] / fl, 3)
             res[f"shards_{name}_over_copy_plus_flat"] = round(
                 med[f"shards_{name}"] / (fl + med[f"copy_{name}"]), 3)
+            if args.bits4:
+                res[f"shards_{name}_over_int8"] = round(
+                    med[f"shards_{name}"] / med[f"int8_{name}"], 3)
         print(json.dumps(res), flush=True)
 
 
@@ -171,9 +193,11 @@ def request(args):
         own = flat_grad[rank * shard:(rank + 1) * shard]
         recv = torch.zeros(shard, dtype=tdt, device="cuda")
         flat_req = mx.PersistentRequest(d, "reduce_scatter", shard, dtype=args.dtype, op="sum",
-                                        group="data", quantized=True, algo=args.algo)
+                                        group="data", quantized=True, algo=args.algo,
+                                        bits=4 if args.bits4 else 8)
         seg_req = mx.SegmentedReduceScatter(d, counts, shard=shard, dtype=args.dtype,
-                                            group="data", algo=args.algo)
+                                            group="data", algo=args.algo,
+                                            compression="int4" if args.bits4 else "int8")
 
         def copy_flat():
             for g, a, b in zip(grads, offs[:-1], offs[1:]):
@@ -212,7 +236,8 @@ def request(args):
             for k, fn in variants.items():
                 times[k].append(timed(fn))
         if rank == 0:
-            res = {"config": "quant-rs-seg-request", "dtype": args.dtype, "layout": name,
+            res = {"config": "quant-rs-seg-request", "bits": 4 if args.bits4 else 8,
+                   "dtype": args.dtype, "layout": name,
                    "total_mib": total * es >> 20, "tensors": len(counts), "world": size,
                    "algo": args.algo or "default", "iters": args.iters, "rounds": args.rounds,
                    "elements_differing_from_copy_flat": differing,
@@ -234,6 +259,7 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--layout", default="both", choices=["both", "aligned64", "ragged4096"])
     ap.add_argument("--algo", default=None, choices=["ring", "direct"])
+    ap.add_argument("--bits4", action="store_true", help="the int4 wire (direct only)")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)

@@ -697,19 +697,31 @@ class SegmentedReduceScatter:
     the value in use); anything smaller is refused.
     algo: None takes MLSL_QUANT_RS_ALGO (ring unless set); "ring" or "direct"
     names it (direct: at most 8 ranks).
+    compression: "int8", or "int4" for the 4-bit wire (block / 2 + 8 bytes a
+    block where int8 takes block + 8): bit for bit the flat ``bits=4`` request
+    on V', the residual included. It runs direct only: algo=None means direct
+    whatever MLSL_QUANT_RS_ALGO says, "ring" is refused, as are more than 8
+    ranks and a block that is no multiple of 8.
     Refused at creation: any other dtype, an empty list, a zero count,
     ``shard * N < total``, a compression plugin.
     ``ShardedOptimizer(grads="in_place")`` reduces its gradients with one such
     request."""
 
-    def __init__(self, dist, counts, shard=None, dtype="f32", group="global", algo=None):
+    def __init__(self, dist, counts, shard=None, dtype="f32", group="global", algo=None,
+                 compression="int8"):
         if algo is not None and algo not in QUANT_RS_ALGO:
             raise ValueError(f"algo={algo!r}: expected None, 'ring' or 'direct'")
+        if compression not in ("int8", "int4"):
+            raise ValueError(f"compression={compression!r}: expected 'int8' or 'int4'")
         L = lib()
         if not hasattr(L, "_rs_segments_declared"):
             P = ctypes.POINTER
             L.mlsl_persistent_reduce_scatter_quantized_segments.argtypes = [
                 c_void_p, P(c_size_t), c_size_t, c_size_t, c_int, c_int, c_int, P(c_void_p)]
+            L.mlsl_persistent_reduce_scatter_quantized_segments_bits.argtypes = [
+                c_void_p, P(c_size_t), c_size_t, c_size_t, c_int, c_int, c_int, c_int,
+                P(c_void_p)]
+            L.mlsl_persistent_reduce_scatter_quantized_segments_bits.restype = c_int
             L.mlsl_request_start_segments_recv.argtypes = [c_void_p, P(c_void_p), c_size_t,
                                                            c_void_p]
             L.mlsl_request_wait.argtypes = [c_void_p, P(c_void_p)]
@@ -727,9 +739,16 @@ class SegmentedReduceScatter:
         # 0 is the C API's spelling of the default
         self.shard = int(shard) if shard else (sum(counts) + world - 1) // world
         h = c_void_p()
-        check(L.mlsl_persistent_reduce_scatter_quantized_segments(
-            dist._h, _sizes(counts), len(counts), self.shard, DTYPE[dtype], GROUP[group],
-            -1 if algo is None else QUANT_RS_ALGO[algo], ctypes.byref(h)))
+        algo = -1 if algo is None else QUANT_RS_ALGO[algo]
+        if compression == "int4":
+            # "ring" raises the library's message
+            check(L.mlsl_persistent_reduce_scatter_quantized_segments_bits(
+                dist._h, _sizes(counts), len(counts), self.shard, DTYPE[dtype], GROUP[group],
+                algo, 4, ctypes.byref(h)))
+        else:
+            check(L.mlsl_persistent_reduce_scatter_quantized_segments(
+                dist._h, _sizes(counts), len(counts), self.shard, DTYPE[dtype], GROUP[group],
+                algo, ctypes.byref(h)))
         self._h = h
         self._ptrs = (c_void_p * max(1, len(counts)))()
 

@@ -469,6 +469,34 @@ int mlsl_persistent_reduce_scatter_quantized_segments(mlsl_distribution d,
     C_CATCH
 }
 
+int mlsl_persistent_reduce_scatter_quantized_segments_bits(mlsl_distribution d,
+                                                           const size_t* counts, size_t nseg,
+                                                           size_t shard, mlsl_data_type dt,
+                                                           mlsl_group g, int algo, int bits,
+                                                           mlsl_request* out) {
+    C_TRY
+    MLSL_CHECK(DT(dt) == DataType::F32 || DT(dt) == DataType::BF16,
+               "quantized reduce_scatter over a tensor list supports f32/bf16 only");
+    MLSL_CHECK(nseg > 0 && counts != nullptr,
+               "quantized reduce_scatter over a tensor list needs at least one tensor "
+               "(nseg == 0)");
+    MLSL_CHECK(algo >= -1 && algo <= 1, "unknown quantized reduce_scatter algorithm");
+    std::unique_ptr<CommRequest> r(NewPersistent(d, g, dt));
+    r->AddReduceScatterSegments(std::vector<size_t>(counts, counts + nseg), shard);
+    // the environment's block size, this request's payload bits
+    QuantParams qp = Environment::GetEnv().GetQuantizationParams();
+    qp.bits = bits;
+    r->SetCompression(Compression::QUANT_INT8, qp);
+    // -1 names no algorithm: direct at 4 bits, MLSL_QUANT_RS_ALGO at 8
+    if (algo >= 0)
+        r->SetQuantRsAlgo(algo == 1 ? QuantRsAlgo::DIRECT : QuantRsAlgo::RING);
+    else if (bits == 8)
+        r->SetQuantRsAlgo(GlobalConfig().quant_rs_algo);
+    r->Setup();
+    *out = r.release();
+    C_CATCH
+}
+
 int mlsl_request_start_segments_recv(mlsl_request req, void* const* ptrs, size_t nseg,
                                      void* recv) {
     C_TRY static_cast<CommRequest*>(req)->StartSegmentsRecv(ptrs, nseg, recv);

@@ -505,6 +505,48 @@ int mlsl_host_quantize_gather_shards(const void* const* ptrs, const size_t* coun
     OPS_CATCH
 }
 
+// The same three on the int4 wire; path as in mlsl_hip_quantize4.
+int mlsl_hip_quantize_gather_shards4(const void* const* ptrs, const size_t* counts,
+                                     size_t nseg, void* err, void* wire, size_t nshards,
+                                     size_t shard, size_t wire_stride, size_t block, int dt,
+                                     int use_err, int path) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_hip_quantize_gather_shards4", 4);
+    size_t total = 0;
+    const std::vector<uint64_t> offs =
+        SegOffsets(counts, nseg, &total, "quantize-gather-shards");
+    DevSegTables tab(offs, ptrs);
+    LaunchQuantizeGatherShards4(tab.ptrs, tab.offs, nseg, err, wire, total, nshards, shard,
+                                wire_stride, block, static_cast<DataType>(dt), use_err != 0,
+                                nullptr, static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_quantize_gather_shards4_tables(const void* const* dev_ptrs,
+                                            const uint64_t* dev_offs, size_t nseg, void* err,
+                                            void* wire, size_t total, size_t nshards,
+                                            size_t shard, size_t wire_stride, size_t block,
+                                            int dt, int use_err, int path) {
+    OPS_TRY LaunchQuantizeGatherShards4(dev_ptrs, dev_offs, nseg, err, wire, total, nshards,
+                                        shard, wire_stride, block, static_cast<DataType>(dt),
+                                        use_err != 0, nullptr, static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_host_quantize_gather_shards4(const void* const* ptrs, const size_t* counts,
+                                      size_t nseg, void* err, void* wire, size_t nshards,
+                                      size_t shard, size_t wire_stride, size_t block, int dt,
+                                      int use_err) {
+    OPS_TRY CheckQuantBlock(block, "mlsl_host_quantize_gather_shards4", 4);
+    size_t total = 0;
+    const std::vector<uint64_t> offs =
+        SegOffsets(counts, nseg, &total, "quantize-gather-shards");
+    HostQuantizeGatherShards(ptrs, offs.data(), nseg, err, wire, total, nshards, shard,
+                             wire_stride, block, static_cast<DataType>(dt), use_err != 0, 4);
+    OPS_CATCH
+}
+
 int mlsl_host_quantize_gather(const void* const* ptrs, const size_t* counts, size_t nseg,
                               void* err, void* wire, size_t block, int dt, int use_err) {
     OPS_TRY CheckQuantBlock(block, "mlsl_host_quantize_gather");

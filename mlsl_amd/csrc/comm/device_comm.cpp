@@ -664,8 +664,14 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
         std::memcpy(st.seg_ptrs_pin, req->SegPtrs().data(), nseg * sizeof(void*));
         HIP_CHECKD(hipMemcpyAsync(seg_ptrs, st.seg_ptrs_pin, nseg * sizeof(void*),
                                   hipMemcpyHostToDevice, s));
-        if (seg_rs)
+        if (seg_rs && p.bits == 4)
             // all N shards of the padded concatenation in one launch
+            LaunchQuantizeGatherShards4(seg_ptrs, seg_offs, nseg,
+                                        p.residual ? base + p.err_off : nullptr,
+                                        base + p.send_seg * p.seg_wire,
+                                        static_cast<size_t>(req->SegOffs().back()), p.nseg,
+                                        p.count, p.seg_wire, p.block, dt, p.residual, s);
+        else if (seg_rs)
             LaunchQuantizeGatherShards(seg_ptrs, seg_offs, nseg,
                                        p.residual ? base + p.err_off : nullptr,
                                        base + p.send_seg * p.seg_wire,
@@ -682,9 +688,9 @@ void IssueCompressed(CommRequest* req, const DeviceReqState& st, const ChunkExec
                                  base + p.send_seg * p.seg_wire, p.count, p.block, dt,
                                  p.residual, s);
     } else {
-        // p.bits == 4: the int4 codec (two-shot allreduce, flat or over a list,
-        // flat direct reduce-scatter and accumulating all-gather only; Setup()
-        // refused everything else)
+        // p.bits == 4: the int4 codec (two-shot allreduce and direct
+        // reduce-scatter, each flat or over a list, and accumulating all-gather
+        // only; Setup() refused everything else)
         for (size_t j = 0; j < p.nseg; ++j) {
             const uint8_t* in = sbuf + j * p.seg_bytes;
             uint8_t* err = p.residual ? base + p.err_off + j * p.seg_bytes : nullptr;

@@ -360,14 +360,14 @@ void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, s
 void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_offs,
                               size_t nseg, void* err, void* wire, size_t total,
                               size_t nshards, size_t shard, size_t wire_stride, size_t block,
-                              DataType dt, bool use_err) {
-    CheckQuantBlock(block, "HostQuantizeGatherShards");
+                              DataType dt, bool use_err, int bits) {
+    CheckQuantBlock(block, "HostQuantizeGatherShards", bits);
     CheckSegTables(seg_ptrs, seg_offs, nseg, total, dt, "quantize-gather-shards");
     MLSL_CHECK(nshards >= 1 && shard >= (total + nshards - 1) / nshards,
                "quantize-gather-shards: shard * nshards < total (the shards do not hold "
                "the tensors)");
     MLSL_CHECK(wire_stride % 4 == 0 &&
-                   wire_stride >= (shard + block - 1) / block * (block + kWireHdr),
+                   wire_stride >= (shard + block - 1) / block * WireBlock(block, bits),
                "quantize-gather-shards: wire_stride is smaller than one shard's wire or "
                "no multiple of 4");
     MLSL_CHECK(!use_err || err != nullptr, "quantize-gather-shards: use_err without err");
@@ -390,7 +390,7 @@ void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_o
                     return i >= total ? 0.f : ue ? in(i) + e[i] : in(i);
                 },
                 [&](size_t i, float v) { if (i + lo < total) e[i + lo] = v; }, w, shard,
-                block, use_err);
+                block, use_err, bits);
         } else {
             uint16_t* e = static_cast<uint16_t*>(err);
             auto in = [&](size_t i) {
@@ -403,7 +403,7 @@ void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_o
                     return i >= total ? 0.f : ue ? in(i) + Bf16F(e[i]) : in(i);
                 },
                 [&](size_t i, float v) { if (i + lo < total) e[i + lo] = F32B(v); }, w, shard,
-                block, use_err);
+                block, use_err, bits);
         }
     }
 }

@@ -81,11 +81,13 @@ void HostQuantizeGather(const void* const* seg_ptrs, const uint64_t* seg_offs, s
 // bytes; the bytes between two wires are not written. An element at or past
 // `total` quantizes as 0, is read through no pointer, and its residual is
 // neither read nor written. Bit for bit what LaunchQuantizeGatherShards
-// computes.
+// computes; at bits = 4 (block a multiple of 8, a shard's wire NumBlocks(shard)
+// * (block / 2 + 8) bytes) what LaunchQuantizeGatherShards4 does, the residual
+// being its one explicit fma(-q, scale, v).
 void HostQuantizeGatherShards(const void* const* seg_ptrs, const uint64_t* seg_offs,
                               size_t nseg, void* err, void* wire, size_t total,
                               size_t nshards, size_t shard, size_t wire_stride, size_t block,
-                              DataType dt, bool use_err);
+                              DataType dt, bool use_err, int bits = 8);
 // Scatter: every element becomes (q * scale) * post_scale, both products
 // rounded to float and one final rounding for bf16; with post_scale == 1.0f
 // the bits of HostDequantize. Only the tensors are written. Bit for bit what

@@ -287,9 +287,6 @@ void CommRequest::BuildChunks() {
                        "the 4-bit wire codec is not wired to the assigning all_gather (15 "
                        "levels per block would be all a gathered value keeps); the 4-bit "
                        "all_gather exists with accumulate only; use bits=8");
-            MLSL_CHECK(!SegmentedReduceScatter(),
-                       "the 4-bit wire codec is not wired to the reduce_scatter over a tensor "
-                       "list (the all_reduce over a tensor list is); use bits=8");
             MLSL_CHECK(Compressed(),
                        "the 4-bit wire codec serves all_reduce and reduce_scatter sums and "
                        "the accumulating all_gather, of f32/bf16 only");
@@ -830,7 +827,8 @@ bool CommRequest::AdvanceHost(Mesh* mesh) {
                                          qp.residual ? wire + qp.err_off : nullptr,
                                          wire + qp.send_seg * qp.seg_wire,
                                          static_cast<size_t>(seg_offs_.back()), qp.nseg,
-                                         qp.count, qp.seg_wire, qp.block, dtype_, qp.residual);
+                                         qp.count, qp.seg_wire, qp.block, dtype_, qp.residual,
+                                         qp.bits);
             else if (Segmented())
                 HostQuantizeGather(seg_ptrs_.data(), seg_offs_.data(), seg_ptrs_.size(),
                                    qp.residual ? wire + qp.err_off : nullptr,

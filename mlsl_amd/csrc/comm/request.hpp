@@ -138,10 +138,10 @@ class CommRequest {
     // do not requantize hop by hop: an ALLREDUCE runs TWO_SHOT and a
     // REDUCE_SCATTER runs DIRECT unless SetQuant*Algo names it, whatever
     // MLSL_QUANT_AR_ALGO / MLSL_QUANT_RS_ALGO say, and Setup() fails for the ring,
-    // for the reduce-scatter over a tensor list, with a plugin, on more than 8
-    // ranks (the two sums), for a block that is no multiple of 8 and for bits
-    // other than 4 or 8. The allreduce over a tensor list runs at 4 bits,
-    // two-shot. An ALLGATHER runs at 4 bits exactly with SetQuantAccumulate(true),
+    // with a plugin, on more than 8 ranks (the two sums), for a block that is no
+    // multiple of 8 and for bits other than 4 or 8. The allreduce and the
+    // reduce-scatter over a tensor list run at 4 bits under the same rules,
+    // two-shot and direct. An ALLGATHER runs at 4 bits exactly with SetQuantAccumulate(true),
     // on any number of ranks (nothing there takes N wires at once): assigning
     // would leave a gathered value 15 levels per block, and Setup() fails for it.
     void SetCompression(Compression c, const QuantParams& qp);

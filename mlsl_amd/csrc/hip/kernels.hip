@@ -2671,6 +2671,118 @@ __global__ void DequantizeScatter4Kernel(const uint8_t* __restrict__ wire, T* co
     });
 }
 
+// The prologue of the reduce-scatter over a list on the int4 wire:
+// QuantizeGather4Kernel's split of work (a lane owns whole payload words, one
+// word per lane kept in registers across the maximum) on the block grid of
+// QuantizeGatherShardsKernel (V' is V followed by zeros up to nshards * shard;
+// wire block `blk` of the launch is block blk % bps of shard blk / bps, at wire
+// + j * wire_stride, so bases ascend with blk and the cursors only move
+// forward). What is new against both:
+//  - a block's base j * shard + b * block is a multiple of nothing, so a word's
+//    tensor address and its residual address err + base + 8w are each looked at
+//    for 16-byte alignment per word (GatherWord4 and QuantizeWord4 do);
+//  - a block has three lengths: block_elems on the wire, n inside its shard (the
+//    shard's partial last block, any number), and `real` <= n elements that
+//    exist. A word's nv counts real elements only; the nibbles past them are 0,
+//    and neither the table nor the residual is touched for them;
+//  - a block at or past `total` is padding only: scale QScale(0), zero payload,
+//    no table access, no Seek, no residual access. It returns early, before
+//    any table access, as in QuantizeGatherShardsKernel and for the reason
+//    recorded there;
+//  - X2: the two blocks of a pair may lie in different shards (bps odd), and
+//    the upper one may be padding while the lower is not (never the reverse:
+//    bases ascend). The wave seeks the lower block's tensor while uniform, the
+//    halves part after that, and only HalfWaveMax, which stays inside a half,
+//    follows.
+template <typename T, bool USE_ERR, bool X2>
+__global__ void QuantizeGatherShards4Kernel(const T* const* __restrict__ ptrs, SegTable tab,
+                                            T* __restrict__ err, uint8_t* __restrict__ wire,
+                                            size_t total, uint32_t nshards, size_t shard,
+                                            size_t wire_stride, size_t block_arg) {
+    constexpr int TEAM = X2 ? 32 : 64;   // lanes per block
+    const size_t block_elems = X2 ? kFastBlock : block_arg;
+    const size_t words = block_elems / 8;
+    const uint32_t bps = static_cast<uint32_t>((shard + block_elems - 1) / block_elems);
+    // the launcher keeps the block count in 32 bits
+    const uint32_t nblocks = nshards * bps;
+    SegCursor<const T> cur;
+    ForEachWaveBlock(X2 ? (static_cast<size_t>(nblocks) + 1) / 2 : nblocks,
+                     [&](size_t vunit, int lane) {
+        // uniform across the wave: the (lower) block's place and the bisection
+        // stay in scalar registers
+        const uint32_t first =
+            __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(vunit)) * (X2 ? 2 : 1);
+        const uint32_t j0 = first / bps, b0 = first - j0 * bps;
+        const size_t base0 = static_cast<size_t>(j0) * shard +
+                             static_cast<size_t>(b0) * block_elems;
+        // the lane's own block: a pair's upper block may open the next shard
+        const bool upper = X2 && lane >= 32;
+        const uint32_t blk = first + (upper ? 1 : 0);
+        const uint32_t b = upper ? (b0 + 1 == bps ? 0 : b0 + 1) : b0;
+        const uint32_t j = upper && b == 0 ? j0 + 1 : j0;
+        const size_t sub = X2 ? (lane & 31) : lane;
+        const size_t in_shard = static_cast<size_t>(b) * block_elems;
+        const size_t base = static_cast<size_t>(j) * shard + in_shard;
+        uint8_t* wblock = wire + j * wire_stride + b * Wire4BlockBytes(block_elems);
+        uint32_t* payload = reinterpret_cast<uint32_t*>(wblock + kWireHdr);
+        auto padding = [&] {
+            if (sub == 0) WriteWireHeader(wblock, QScale<kQ4Max>(0.f));
+            for (size_t w = sub; w < words; w += TEAM) payload[w] = 0;
+        };
+        if (base0 >= total) {
+            // the whole unit is padding: nothing is read, the table included
+            if (blk < nblocks) padding();
+            return;
+        }
+        cur.Seek(tab, ptrs, base0);
+        if (blk >= nblocks) return;   // the idle half of the last pair
+        if (X2 && base >= total) {
+            // the upper half alone: the lower goes on without it
+            padding();
+            return;
+        }
+        // the block's elements that exist: at least one from here on
+        const size_t n = min(block_elems, shard - in_shard);
+        const size_t real = min(n, total - base);
+        auto valid = [&](size_t w) {
+            return w * 8 >= real ? 0 : static_cast<int>(min(size_t(8), real - w * 8));
+        };
+        auto eb = [&](size_t w) { return USE_ERR ? err + base + w * 8 : nullptr; };
+        auto team_max = [&](float m) { return X2 ? HalfWaveMax(m) : WaveMax(m); };
+        LaneSeg<const T> ls(cur);
+        float v[8];
+        if (words <= TEAM) {
+            // one word per lane: read once, kept across the maximum
+            const int nv = sub < words ? valid(sub) : 0;
+            GatherWord4<T, USE_ERR>(tab, ptrs, ls, base + sub * 8, nv, eb(sub), v);
+            float m = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf(v[k]));
+            const float scale = QScale<kQ4Max>(team_max(m));
+            if (sub == 0) WriteWireHeader(wblock, scale);
+            if (sub < words)
+                payload[sub] = QuantizeWord4<T, USE_ERR>(v, scale, 1.f / scale, nv, eb(sub));
+        } else {
+            float m = 0.f;
+            for (size_t w = sub; w * 8 < real; w += TEAM) {
+                GatherWord4<T, USE_ERR>(tab, ptrs, ls, base + w * 8, valid(w), eb(w), v);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf(v[k]));
+            }
+            const float scale = QScale<kQ4Max>(team_max(m));
+            if (sub == 0) WriteWireHeader(wblock, scale);
+            const float inv = 1.f / scale;
+            ls = LaneSeg<const T>(cur);
+            // a word past the real elements gathers nothing and packs as 0
+            for (size_t w = sub; w < words; w += TEAM) {
+                const int nv = valid(w);
+                GatherWord4<T, USE_ERR>(tab, ptrs, ls, base + w * 8, nv, eb(w), v);
+                payload[w] = QuantizeWord4<T, USE_ERR>(v, scale, inv, nv, eb(w));
+            }
+        }
+    });
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -2705,6 +2817,47 @@ void LaunchQuantizeGather4(const void* const* seg_ptrs, const uint64_t* seg_offs
                     <<<grid, dim3(kBlock), 0, stream>>>(
                         reinterpret_cast<const T* const*>(seg_ptrs), tab, e, w, count,
                         block_elems);
+            });
+        });
+    };
+    if (dt == DataType::F32) launch(static_cast<float*>(err));
+    else launch(static_cast<unsigned short*>(err));
+    HIP_CHECK(hipGetLastError());
+}
+
+void LaunchQuantizeGatherShards4(const void* const* seg_ptrs, const uint64_t* seg_offs,
+                                 size_t nseg, void* err, void* wire, size_t total,
+                                 size_t nshards, size_t shard, size_t wire_stride,
+                                 size_t block_elems, DataType dt, bool use_err,
+                                 hipStream_t stream, Quant4Path path) {
+    CheckQuantBlock(block_elems, "LaunchQuantizeGatherShards4", 4);
+    CheckSegArgs(seg_ptrs, seg_offs, nseg, total, dt, "int4 quantize-gather-shards");
+    MLSL_CHECK(nshards >= 1 && shard >= (total + nshards - 1) / nshards,
+               "int4 quantize-gather-shards: shard * nshards < total (the shards do not "
+               "hold the tensors)");
+    const size_t bps = NumBlocks(shard, block_elems);
+    const size_t nblocks = bps * nshards;
+    MLSL_CHECK(nblocks <= 0xffffffffull,
+               "int4 quantize-gather-shards: more than 2^32 wire blocks");
+    MLSL_CHECK(wire_stride % 4 == 0 && wire_stride >= bps * Wire4BlockBytes(block_elems),
+               "int4 quantize-gather-shards: wire_stride is smaller than one shard's wire "
+               "or no multiple of 4");
+    MLSL_CHECK((reinterpret_cast<uintptr_t>(wire) & 3) == 0,
+               "int4 quantize-gather-shards: the wire must be 4-byte aligned");
+    MLSL_CHECK(!use_err || err != nullptr,
+               "int4 quantize-gather-shards: use_err without err");
+    const bool fast = TakeSegFast4(path, block_elems, "LaunchQuantizeGatherShards4");
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const dim3 grid = fast ? PairGrid(nblocks) : WaveGrid(nblocks);
+    uint8_t* w = static_cast<uint8_t*>(wire);
+    auto launch = [&](auto* e) {
+        using T = std::remove_pointer_t<decltype(e)>;
+        DispatchBool(use_err, [&](auto ue) {
+            DispatchBool(fast, [&](auto x2) {
+                QuantizeGatherShards4Kernel<T, decltype(ue)::value, decltype(x2)::value>
+                    <<<grid, dim3(kBlock), 0, stream>>>(
+                        reinterpret_cast<const T* const*>(seg_ptrs), tab, e, w, total,
+                        static_cast<uint32_t>(nshards), shard, wire_stride, block_elems);
             });
         });
     };

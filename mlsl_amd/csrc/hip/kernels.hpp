@@ -197,6 +197,26 @@ void LaunchDequantizeScatter4(const void* wire, void* const* seg_ptrs,
                               size_t block_elems, DataType dt, float post_scale,
                               bool round_first, hipStream_t stream,
                               Quant4Path path = Quant4Path::AUTO);
+// LaunchQuantizeGatherShards on the int4 wire: the prologue of the 4-bit
+// reduce-scatter over a list. For every shard j of V', one launch writes to
+// wire + j * wire_stride exactly the bytes LaunchQuantize4 writes for V'[j *
+// shard, (j + 1) * shard), and with use_err the residual (its one explicit fma)
+// to err + j * shard, flat in V' order. wire_stride is a multiple of 4 and at
+// least NumBlocks(shard) * (block_elems / 2 + 8); the bytes between two shards'
+// wires are not written. An element at or past `total` is the value 0 and is
+// read through no pointer; its residual is neither read nor written, and a wire
+// block that holds no real element gets scale 1 and a zero payload without any
+// table access. block_elems is a non-zero multiple of 8, the wire 4-byte
+// aligned, the tensors aligned to their element only. Paths as for
+// LaunchQuantizeGather4: GENERIC one wave per wire block, FAST (block 256, it
+// throws elsewhere) one block per half-wave, the two blocks of a pair possibly
+// in different shards; AUTO takes FAST at block 256. Quant4BlocksPerTrip
+// holds. The host twin is HostQuantizeGatherShards at bits = 4.
+void LaunchQuantizeGatherShards4(const void* const* seg_ptrs, const uint64_t* seg_offs,
+                                 size_t nseg, void* err, void* wire, size_t total,
+                                 size_t nshards, size_t shard, size_t wire_stride,
+                                 size_t block_elems, DataType dt, bool use_err,
+                                 hipStream_t stream, Quant4Path path = Quant4Path::AUTO);
 // LaunchDequantizeSegments on the int4 wire: the finish of the 4-bit
 // all-gather. `wire` holds nseg segment wires of NumBlocks(count) int4 blocks
 // each, back to back (wire block idx of the launch at idx * (block_elems / 2 +

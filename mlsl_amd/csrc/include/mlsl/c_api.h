@@ -131,9 +131,9 @@ int mlsl_persistent_all_reduce_quantized_algo(mlsl_distribution d, size_t count,
  * algorithms), and the ring fails at creation: it requantizes on every hop,
  * which at 4 bits loses far more than at 8. Also failing at creation at 4
  * bits: a group of more than 8 ranks, a compression plugin, a block that is
- * no multiple of 8; and any bits other than 4 or 8. The reduce-scatter over a
- * tensor list has no 4-bit form; the allreduce over a tensor list has one
- * (mlsl_persistent_all_reduce_quantized_segments_bits). */
+ * no multiple of 8; and any bits other than 4 or 8. Both have a 4-bit form
+ * over a tensor list (mlsl_persistent_all_reduce_quantized_segments_bits,
+ * mlsl_persistent_reduce_scatter_quantized_segments_bits). */
 int mlsl_persistent_all_reduce_quantized_bits(mlsl_distribution d, size_t count,
                                               mlsl_data_type dt, mlsl_reduction op,
                                               mlsl_group g, int algo, int bits,
@@ -258,6 +258,19 @@ int mlsl_persistent_reduce_scatter_quantized_segments(mlsl_distribution d,
                                                       size_t shard, mlsl_data_type dt,
                                                       mlsl_group g, int algo,
                                                       mlsl_request* out);
+/* The same request with the payload bits of its wire named: bits == 8 is the
+ * function above. bits == 4 is the int4 wire of
+ * mlsl_persistent_reduce_scatter_quantized_bits, with that function's rules:
+ * it runs direct only (algo -1 or 1, MLSL_QUANT_RS_ALGO is not read; 0, the
+ * ring, fails at creation), on at most 8 ranks, without a plugin, with a block
+ * that is a multiple of 8. Bit for bit the flat bits == 4 request with
+ * recv_count = shard on V'; the residual (N * shard elements) is pinned
+ * exactly (one fma). Started with mlsl_request_start_segments_recv. */
+int mlsl_persistent_reduce_scatter_quantized_segments_bits(mlsl_distribution d,
+                                                           const size_t* counts, size_t nseg,
+                                                           size_t shard, mlsl_data_type dt,
+                                                           mlsl_group g, int algo, int bits,
+                                                           mlsl_request* out);
 int mlsl_request_start_segments_recv(mlsl_request req, void* const* ptrs, size_t nseg,
                                      void* recv);
 int mlsl_persistent_all_gather(mlsl_distribution d, size_t send_count, mlsl_data_type dt,

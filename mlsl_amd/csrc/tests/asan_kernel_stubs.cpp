@@ -105,6 +105,7 @@ void LaunchDequantizeSegments(const void* w, size_t nseg, void* out, size_t n, s
 void LaunchQuantizeGather(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGather, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st)
 void LaunchQuantizeGatherShards(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t total, size_t nshards, size_t shard, size_t stride, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGatherShards, ptrs, offs, nseg, err, w, total, nshards, shard, stride, blk, dt, use_err, st)
 void LaunchDequantizeScatter(const void* w, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, size_t blk, DataType dt, float post, bool round_first, hipStream_t st) STUB(LaunchDequantizeScatter, w, ptrs, offs, nseg, n, blk, dt, post, round_first, st)
+void LaunchQuantizeGatherShards4(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t total, size_t nshards, size_t shard, size_t stride, size_t blk, DataType dt, bool use_err, hipStream_t st, Quant4Path path) STUB(LaunchQuantizeGatherShards4, ptrs, offs, nseg, err, w, total, nshards, shard, stride, blk, dt, use_err, st, path)
 void LaunchQuantizeGather4(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st, Quant4Path path) STUB(LaunchQuantizeGather4, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st, path)
 void LaunchDequantizeScatter4(const void* w, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, size_t blk, DataType dt, float post, bool round_first, hipStream_t st, Quant4Path path) STUB(LaunchDequantizeScatter4, w, ptrs, offs, nseg, n, blk, dt, post, round_first, st, path)
 void LaunchDequantizeSegments4(const void* w, size_t nseg, void* out, size_t n, size_t blk, DataType dt, bool acc, hipStream_t st, Quant4Path path) STUB(LaunchDequantizeSegments4, w, nseg, out, n, blk, dt, acc, st, path)

@@ -132,8 +132,16 @@ def _lib():
         L.mlsl_hip_quantize_gather_shards_tables.argtypes = [
             c.c_void_p, c.c_void_p, c.c_size_t, c.c_void_p, c.c_void_p, c.c_size_t,
             c.c_size_t, c.c_size_t, c.c_size_t, c.c_size_t, c.c_int, c.c_int]
+        L.mlsl_hip_quantize_gather_shards4.argtypes = \
+            L.mlsl_hip_quantize_gather_shards.argtypes + [c.c_int]
+        L.mlsl_hip_quantize_gather_shards4_tables.argtypes = \
+            L.mlsl_hip_quantize_gather_shards_tables.argtypes + [c.c_int]
+        L.mlsl_host_quantize_gather_shards4.argtypes = \
+            L.mlsl_hip_quantize_gather_shards.argtypes
         for n in ("mlsl_hip_quantize_gather_shards", "mlsl_host_quantize_gather_shards",
-                  "mlsl_hip_quantize_gather_shards_tables"):
+                  "mlsl_hip_quantize_gather_shards_tables",
+                  "mlsl_hip_quantize_gather_shards4", "mlsl_host_quantize_gather_shards4",
+                  "mlsl_hip_quantize_gather_shards4_tables"):
             getattr(L, n).restype = c.c_int
         for n in ("mlsl_hip_quantize_gather", "mlsl_host_quantize_gather",
                   "mlsl_hip_dequantize_scatter", "mlsl_host_dequantize_scatter"):
@@ -489,14 +497,14 @@ def dequantize_scatter4_tables(wire, dev_ptrs, dev_offs, nseg, count, block=256,
                                                      1 if round_first else 0, _PATH4[path]))
 
 
-def _shard_args(total, nshards, shard, wire_stride, block):
+def _shard_args(total, nshards, shard, wire_stride, block, bits=8):
     """(nshards, shard, wire_stride) checked; wire_stride=None is one shard's
     wire bytes rounded up to 16."""
     nshards, shard = int(nshards), int(shard)
     if nshards < 1 or shard * nshards < total:
         raise ValueError(f"shard * nshards < total: {nshards} shards of {shard} elements "
                          f"do not hold {total}")
-    need = wire_bytes(shard, block)
+    need = wire_bytes(shard, block, bits)
     if wire_stride is None:
         wire_stride = (need + 15) // 16 * 16
     wire_stride = int(wire_stride)
@@ -541,6 +549,43 @@ def quantize_gather_shards_tables(dev_ptrs, dev_offs, nseg, total, wire, nshards
     check(_lib().mlsl_hip_quantize_gather_shards_tables(
         pp, fp, nseg, ep, wp, total, nshards, shard, wire_stride, block, DTYPE[dtype],
         1 if err is not None else 0))
+
+
+def quantize_gather_shards4(tensors, counts, wire, nshards, shard, err=None, block=256,
+                            dtype=None, wire_stride=None, path=None):
+    """`quantize_gather_shards` into the int4 wire, in one launch: shard j of
+    V' gets exactly the bytes `quantize4` writes for it, at wire + j *
+    wire_stride, and the residual (one fma(-q, scale, v), pinned bit for bit)
+    at err + j * shard. block is a multiple of 8, the wire 4-byte aligned,
+    wire_stride=None is wire_bytes(shard, block, 4) rounded up to 16. Padding
+    as in `quantize_gather_shards`: the value 0, read through no pointer, its
+    residual left alone. path as in `quantize_gather4`; at "fast" the two
+    blocks of a half-wave pair may lie in different shards. This is the
+    prologue of `SegmentedReduceScatter(compression="int4")`."""
+    _check_block4(block)
+    ptrs, cnts, nseg, total, dt = _seg_tables(tensors, counts, dtype)
+    nshards, shard, wire_stride = _shard_args(total, nshards, shard, wire_stride, block, 4)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather_shards4(ptrs, cnts, nseg, ep, wp, nshards, shard,
+                                                  wire_stride, block, DTYPE[dt],
+                                                  1 if err is not None else 0, _PATH4[path]))
+
+
+def quantize_gather_shards4_tables(dev_ptrs, dev_offs, nseg, total, wire, nshards, shard,
+                                   err=None, block=256, dtype="f32", wire_stride=None,
+                                   path=None):
+    """`quantize_gather_shards4` over tables in DEVICE memory; see
+    `quantize_gather_tables` (dev_offs runs from 0 to total)."""
+    _check_block4(block)
+    nshards, shard, wire_stride = _shard_args(total, nshards, shard, wire_stride, block, 4)
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    fp, _ = _as_ptr_dtype(dev_offs)
+    wp, _ = _as_ptr_dtype(wire)
+    ep, _ = _as_ptr_dtype(err)
+    check(_lib().mlsl_hip_quantize_gather_shards4_tables(
+        pp, fp, nseg, ep, wp, total, nshards, shard, wire_stride, block, DTYPE[dtype],
+        1 if err is not None else 0, _PATH4[path]))
 
 
 def quantize_gather_tables(dev_ptrs, dev_offs, nseg, count, wire, err=None, block=256,
@@ -702,6 +747,19 @@ def host_quantize_gather4(arrays, counts, wire, err=None, block=256, dtype="f32"
     ep = None if err is None else _host_buf(err, total * _ELEM_BYTES[dtype], "err")
     check(_lib().mlsl_host_quantize_gather4(ptrs, cnts, nseg, ep, wp, block, DTYPE[dtype],
                                             1 if err is not None else 0))
+
+
+def host_quantize_gather_shards4(arrays, counts, wire, nshards, shard, err=None, block=256,
+                                 dtype="f32", wire_stride=None):
+    """Host twin of `quantize_gather_shards4` on numpy arrays: the same bits."""
+    _check_block4(block)
+    ptrs, cnts, nseg, total = _host_seg_tables(arrays, counts, dtype, "arrays")
+    nshards, shard, wire_stride = _shard_args(total, nshards, shard, wire_stride, block, 4)
+    wp = _host_buf(wire, (nshards - 1) * wire_stride + wire_bytes(shard, block, 4), "wire")
+    ep = None if err is None else _host_buf(err, nshards * shard * _ELEM_BYTES[dtype], "err")
+    check(_lib().mlsl_host_quantize_gather_shards4(ptrs, cnts, nseg, ep, wp, nshards, shard,
+                                                   wire_stride, block, DTYPE[dtype],
+                                                   1 if err is not None else 0))
 
 
 def host_dequantize_scatter4(wire, arrays, counts, block=256, dtype="f32", post_scale=1.0,

@@ -33,7 +33,8 @@ from step to step). The parameter all_gather is exact unless
 With ``grads="in_place"`` on top of that the int8 wire is built straight from
 the gradients where they lie (one ``mx.SegmentedReduceScatter`` over
 ``[p.grad ...]``): the flat gradient buffer, as large as the model, and the
-copy of every gradient into it are gone.
+copy of every gradient into it are gone. The int4 wire is built the same way
+with ``compression="int4", grads="in_place", rs_algo="direct"``.
 """
 import torch
 
@@ -91,9 +92,13 @@ class ShardedOptimizer:
         "int4" is that reduce_scatter on the 4-bit wire (about half the wire
         bytes, 15 levels per block instead of 255, the error fed back the
         same way): PersistentRequest(..., bits=4) on the grads="copy" path.
-        It runs "direct" only: rs_algo may be None or "direct", and "ring"
-        and grads="in_place" are refused (the tensor-list request has no
-        4-bit form); the block size must be a multiple of 8.
+        It runs "direct" only: rs_algo may be None or "direct" and "ring" is
+        refused; the block size must be a multiple of 8. With
+        grads="in_place" the rule is: at 4 bits the in-place path runs direct
+        only, and the caller names the algorithm. rs_algo="direct" creates
+        SegmentedReduceScatter(compression="int4", algo="direct"), which from
+        there behaves as the int8 in-place path does; rs_algo=None is
+        refused.
         rs_algo: algorithm of that quantized reduce_scatter: None
         (MLSL_QUANT_RS_ALGO, ring unless set), "ring", or "direct" (each shard
         goes straight to its owner and is summed once, nothing requantized;
@@ -106,7 +111,8 @@ class ShardedOptimizer:
         size a multiple of 8.
         grads: "copy" gathers every gradient into one flat buffer as large as
         the parameters (``flat_grad``) before it is reduced. "in_place" (needs
-        reduce="rs" and compression="int8"; any rs_algo and ag_compression)
+        reduce="rs" and compression="int8", any rs_algo, or compression="int4"
+        with rs_algo="direct"; any ag_compression)
         keeps no such buffer at world > 1: the quantized reduce_scatter reads
         the gradients where they lie and leaves the owned shard in
         ``own_grad``, a tensor of its own. The parameters' bits are those of
@@ -132,10 +138,10 @@ class ShardedOptimizer:
             raise ValueError('compression="int4" does not run rs_algo="ring": the ring '
                              'requantizes on every hop, which at 4 bits loses far more than '
                              'at 8; use rs_algo=None or "direct"')
-        if compression == "int4" and grads == "in_place":
-            raise ValueError('compression="int4" is not wired to grads="in_place" (the '
-                             'reduce_scatter over a tensor list has no 4-bit form); use '
-                             'grads="copy"')
+        if compression == "int4" and grads == "in_place" and rs_algo is None:
+            raise ValueError('compression="int4" is not wired to grads="in_place" with no '
+                             'algorithm named: at 4 bits the in-place path runs direct only, '
+                             'and naming rs_algo="direct" runs it')
         self.compression = compression
         if rs_algo not in (None, "ring", "direct"):
             raise ValueError(f"rs_algo={rs_algo!r}: expected None, 'ring' or 'direct'")
@@ -152,9 +158,9 @@ class ShardedOptimizer:
         if grads == "in_place" and reduce != "rs":
             raise ValueError('grads="in_place" reads the gradients in the reduce_scatter: '
                              'it needs reduce="rs"')
-        if grads == "in_place" and compression != "int8":
-            raise ValueError('grads="in_place" builds the int8 wire from the gradients: '
-                             'it needs compression="int8"')
+        if grads == "in_place" and compression not in ("int8", "int4"):
+            raise ValueError('grads="in_place" builds the quantized wire from the gradients: '
+                             'it needs compression="int8" (or "int4" with rs_algo="direct")')
         self.grads = grads
 
         if torch.cuda.is_available() and self.params[0].is_cuda:
@@ -211,7 +217,7 @@ class ShardedOptimizer:
         if self._in_place:
             self._qrs_seg = mx.SegmentedReduceScatter(
                 self.dist, [p.numel() for p in self.params], shard=self.shard,
-                dtype=_dt(self.flat), group=group, algo=rs_algo)
+                dtype=_dt(self.flat), group=group, algo=rs_algo, compression=compression)
         elif compression != "none" and self.world > 1:
             self._qrs = mx.PersistentRequest(self.dist, "reduce_scatter", self.shard,
                                              dtype=_dt(self.flat), op="sum",
