@@ -446,6 +446,61 @@ int mlsl_hip_list_elems_per_trip(int dt, size_t* out) {
     OPS_CATCH
 }
 
+// Clipping by the global norm: `out` and `total` are one double in DEVICE
+// memory; the sum of squares goes there and the scale reads it from there.
+int mlsl_hip_sumsq(const void* in, size_t count, int dt, double* out, int accumulate) {
+    OPS_TRY LaunchSumSq(in, count, static_cast<DataType>(dt), out, accumulate != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_sumsq_list(const void* const* ptrs, const size_t* counts, size_t nseg, int dt,
+                        double* out, int accumulate) {
+    OPS_TRY size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "sumsq-list");
+    DevSegTables tab(offs, ptrs);
+    LaunchSumSqList(tab.ptrs, tab.offs, nseg, count, static_cast<DataType>(dt), out,
+                    accumulate != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_sumsq_list_tables(const void* const* dev_ptrs, const uint64_t* dev_offs,
+                               size_t nseg, size_t count, int dt, double* out,
+                               int accumulate) {
+    OPS_TRY LaunchSumSqList(dev_ptrs, dev_offs, nseg, count, static_cast<DataType>(dt), out,
+                            accumulate != 0, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_clip_scale(void* data, size_t count, int dt, const double* total,
+                        float max_norm) {
+    OPS_TRY LaunchClipScale(data, count, static_cast<DataType>(dt), total, max_norm, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_clip_scale_list(void* const* ptrs, const size_t* counts, size_t nseg, int dt,
+                             const double* total, float max_norm) {
+    OPS_TRY size_t count = 0;
+    const std::vector<uint64_t> offs = SegOffsets(counts, nseg, &count, "clip-scale-list");
+    DevSegTables tab(offs, ptrs);
+    LaunchClipScaleList(tab.ptrs, tab.offs, nseg, count, static_cast<DataType>(dt), total,
+                        max_norm, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_hip_clip_scale_list_tables(void* const* dev_ptrs, const uint64_t* dev_offs,
+                                    size_t nseg, size_t count, int dt, const double* total,
+                                    float max_norm) {
+    OPS_TRY LaunchClipScaleList(dev_ptrs, dev_offs, nseg, count, static_cast<DataType>(dt),
+                                total, max_norm, nullptr);
+    SyncNullStream();
+    OPS_CATCH
+}
+
 int mlsl_host_gather_list(const void* const* ptrs, const size_t* counts, size_t nseg,
                           void* flat, int dt) {
     OPS_TRY size_t count = 0;

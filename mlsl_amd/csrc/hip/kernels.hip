@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <mutex>
+#include <string>
 #include <type_traits>
 
 #include "../core/log.hpp"
@@ -3261,6 +3263,294 @@ void LaunchScatterScaleList(const void* flat, void* const* seg_ptrs, const uint6
     // flat is only read: the kernel's scatter arm never stores into it
     LaunchListMove<false>(seg_ptrs, seg_offs, nseg, const_cast<void*>(flat), count, dt,
                           post_scale, stream, "scatter-scale-list");
+}
+
+// ---------------------------------------------------------------------------
+// Clipping by the global L2 norm: the sum of squares of a buffer, or of a list
+// of tensors, into one double in device memory, and the scaling of the same
+// elements by min(1, max_norm / (sqrt(total) + 1e-6)), the total read from
+// device memory by the kernel. The host never sees the norm.
+//
+// Split of work: the exact list kernels' (above). A wave owns a kListTileBytes
+// tile of the concatenation and grid-strides over tiles; a tile is cut into
+// runs at tensor boundaries (the flat forms have one run a tile). Only one
+// address counts here, the tensor's own, so every run goes at 16 bytes from its
+// first 16-byte aligned address on, four loads of a lane in flight, and the up
+// to 16 / sizeof(T) - 1 elements before and after go one element per lane. A
+// tile with more than kListMaxRuns runs hands its remainder to LaneSeg.
+//
+// Sum of squares: an element becomes a double and is squared and added in
+// double, one fma: the square of a 24-bit significand is exact in 53 bits, so
+// the fma rounds only the addition, and an f32 near 1e25 squares to a finite
+// double. A lane keeps one accumulator per load in flight, the four are added
+// in a fixed order, then the wave's 64 by shuffles, then the workgroup's four
+// waves through LDS, and thread 0 stores one double to partials[blockIdx.x]. A
+// second launch of one workgroup adds the at most kMaxGrid partials in a tree
+// that is a function of the index alone (thread t takes partials 8t to 8t + 7
+// in that order, then the same wave and LDS stages) and writes *out. No atomic
+// takes part, so the order of the additions is a function of (count, address
+// mod 16, for a list the table) and two runs give the same bits. The partials
+// are one allocation per device for the process's lifetime, so two launches
+// must not run at once on two streams of a device.
+//
+// Loads of the sum are plain, not nontemporal: the scale reads the same bytes
+// next. The scale's product is ListScale's, one float32 multiplication in a
+// register of its own, rounded once; its stores are plain.
+
+namespace {
+
+// The wave's sum in lane 0: lane i takes lane i + off, off = 32, 16, ... 1.
+__device__ __forceinline__ double WaveSum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// The workgroup's sum, the four waves' sums added in wave order. Every thread
+// of a kBlock workgroup calls it, outside divergent control flow.
+__device__ __forceinline__ double BlockSum(double v) {
+    __shared__ double wave_sum[kBlock / 64];
+    v = WaveSum(v);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+}
+
+// run(p, n, lane) for every run of every tile this wave owns, p at the run's
+// first element and n >= 1; in a tile with more than kListMaxRuns runs,
+// elem(p) for each element past those, lane-strided. Without LIST the buffer
+// at `flat` is the one tensor and no table is read.
+template <typename T, bool LIST, typename Run, typename Elem>
+__device__ __forceinline__ void ForEachTileRun(
+    T* const* __restrict__ ptrs, const SegTable& tab, T* flat, size_t count, Run run,
+    Elem elem, size_t gtid = blockIdx.x * blockDim.x + threadIdx.x,
+    size_t gthreads = gridDim.x * blockDim.x) {
+    constexpr size_t kTile = kListTileBytes / sizeof(T);
+    SegCursor<T> cur;
+    ForEachWaveBlock(
+        (count + kTile - 1) / kTile,
+        [&](size_t vtile, int lane) {
+            const size_t begin = WaveUniform(vtile) * kTile;
+            const size_t end = min(count, begin + kTile);
+            if constexpr (!LIST) {
+                run(flat + begin, end - begin, lane);
+            } else {
+                cur.Seek(tab, ptrs, begin);
+                size_t e = begin;
+                for (int runs = 0; e < end; ++runs) {
+                    if (e >= cur.hi) {
+                        // the table's last entry bounds the walk whatever `count` says
+                        if (cur.seg + 1 >= tab.nseg) return;
+                        ++cur.seg;
+                        cur.lo = cur.hi;
+                        cur.hi = tab.offs[cur.seg + 1];
+                        cur.ptr = ptrs[cur.seg];
+                    }
+                    if (runs == kListMaxRuns) {
+                        LaneSeg<T> ls(cur);
+                        for (size_t i = e + lane; i < end; i += 64) elem(ls.At(tab, ptrs, i));
+                        return;
+                    }
+                    const size_t run_end = min(static_cast<size_t>(cur.hi), end);
+                    run(cur.ptr + (e - cur.lo), run_end - e, lane);
+                    e = run_end;
+                }
+            }
+        },
+        gtid, gthreads);
+}
+
+template <typename T>
+__device__ __forceinline__ double AddSquare(T x, double acc) {
+    const double d = static_cast<double>(Decode(x));
+    return __builtin_fma(d, d, acc);
+}
+
+// The squares of the n >= 1 elements at src onto acc: vector k of a lane's four
+// in flight onto acc[k], head and tail elements onto acc[0].
+template <typename T>
+__device__ __forceinline__ void SumSqRun(const T* src, size_t n, int lane, double (&acc)[4]) {
+    constexpr size_t G = 16 / sizeof(T);
+    size_t head = ((0 - reinterpret_cast<uintptr_t>(src)) & 15) / sizeof(T);
+    if (head > n) head = n;
+    if (static_cast<size_t>(lane) < head) acc[0] = AddSquare(src[lane], acc[0]);
+    const size_t nvec = (n - head) / G;
+    const uint4_ev* sv = reinterpret_cast<const uint4_ev*>(src + head);
+    for (size_t i = lane; i < nvec; i += 256) {
+        uint4_ev v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + 64 * k < nvec) v[k] = sv[i + 64 * k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (i + 64 * k < nvec) {
+                T e[G];
+                __builtin_memcpy(e, &v[k], 16);
+#pragma unroll
+                for (size_t j = 0; j < G; ++j) acc[k] = AddSquare(e[j], acc[k]);
+            }
+        }
+    }
+    const size_t tail = head + nvec * G + lane;
+    if (tail < n) acc[0] = AddSquare(src[tail], acc[0]);
+}
+
+template <typename T, bool LIST>
+__global__ void SumSqKernel(const T* const* __restrict__ ptrs, SegTable tab,
+                            const T* __restrict__ flat, size_t count,
+                            double* __restrict__ partials) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    ForEachTileRun<const T, LIST>(
+        ptrs, tab, flat, count,
+        [&](const T* p, size_t n, int lane) { SumSqRun(p, n, lane, acc); },
+        [&](const T* p) { acc[0] = AddSquare(*p, acc[0]); });
+    const double s = BlockSum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// One workgroup: *out = (accumulate ? *out : 0) + partials[0, n), n <= kMaxGrid.
+__global__ void SumSqFinishKernel(const double* __restrict__ partials, int n, double* out,
+                                  bool accumulate) {
+    constexpr int kPer = kMaxGrid / kBlock;
+    double a = 0.0;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+        const int i = static_cast<int>(threadIdx.x) * kPer + j;
+        if (i < n) a += partials[i];
+    }
+    a = BlockSum(a);
+    if (threadIdx.x == 0) *out = accumulate ? *out + a : a;
+}
+
+// torch's clip coefficient; a NaN total stays NaN (the comparison is false).
+__device__ __forceinline__ float ClipFactor(const double* total, float max_norm) {
+    const double r = static_cast<double>(max_norm) / (sqrt(*total) + 1e-6);
+    return static_cast<float>(r > 1.0 ? 1.0 : r);
+}
+
+template <typename T, bool LIST>
+__global__ void ClipScaleKernel(T* const* __restrict__ ptrs, SegTable tab, T* flat,
+                                size_t count, const double* __restrict__ total,
+                                float max_norm) {
+    using E = typename ListWord<sizeof(T)>::type;
+    const float factor = ClipFactor(total, max_norm);
+    ForEachTileRun<T, LIST>(
+        ptrs, tab, flat, count,
+        // the tensor is both sides of the scatter's run, so always at 16 bytes
+        [&](T* p, size_t n, int lane) { ListMoveRunW<T, 16, true>(p, p, n, factor, lane); },
+        [&](T* p) {
+            E* x = reinterpret_cast<E*>(p);
+            *x = ListScale<T, true>(*x, factor);
+        });
+}
+
+// One buffer of kMaxGrid doubles per device, allocated at the first use and
+// kept for the process's lifetime.
+double* SumSqPartials() {
+    constexpr int kMaxDevices = 64;
+    static std::mutex mu;
+    static double* bufs[kMaxDevices] = {};
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    MLSL_CHECK(dev >= 0 && dev < kMaxDevices, "sumsq: device index out of range");
+    std::lock_guard<std::mutex> lock(mu);
+    if (bufs[dev] == nullptr) {
+        void* p = nullptr;
+        HIP_CHECK(hipMalloc(&p, kMaxGrid * sizeof(double)));
+        bufs[dev] = static_cast<double*>(p);
+    }
+    return bufs[dev];
+}
+
+// The checks the four launchers share; `buf` is the flat forms' buffer.
+template <bool LIST>
+void CheckClipArgs(const void* seg_ptrs, const void* seg_offs, size_t nseg, const void* buf,
+                   size_t count, DataType dt, const double* scalar, const char* where) {
+    if (dt != DataType::F32 && dt != DataType::BF16 && dt != DataType::F16)
+        MLSL_THROW(std::string(where) + " supports f32/bf16/f16 only");
+    if constexpr (LIST) {
+        MLSL_CHECK(nseg >= 1 && nseg <= 0xffffffffull && count >= nseg,
+                   std::string(where) + " takes at least one segment of at least one element");
+        MLSL_CHECK(seg_ptrs != nullptr && seg_offs != nullptr,
+                   std::string(where) + ": null segment table");
+    } else {
+        MLSL_CHECK(count >= 1, std::string(where) + " takes at least one element");
+        MLSL_CHECK(buf != nullptr &&
+                       (reinterpret_cast<uintptr_t>(buf) & (DtypeSize(dt) - 1)) == 0,
+                   std::string(where) + ": the buffer must be aligned to its element");
+    }
+    MLSL_CHECK(scalar != nullptr && (reinterpret_cast<uintptr_t>(scalar) & 7) == 0,
+               std::string(where) + ": the f64 scalar must be 8-byte aligned device memory");
+}
+
+template <typename F>
+void DispatchListDtype(DataType dt, F&& f) {
+    if (dt == DataType::F32) f(static_cast<float*>(nullptr));
+    else if (dt == DataType::BF16) f(static_cast<unsigned short*>(nullptr));
+    else f(static_cast<__half*>(nullptr));
+}
+
+template <bool LIST>
+void LaunchSumSqAny(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                    const void* in, size_t count, DataType dt, double* out, bool accumulate,
+                    hipStream_t stream, const char* where) {
+    CheckClipArgs<LIST>(seg_ptrs, seg_offs, nseg, in, count, dt, out, where);
+    double* partials = SumSqPartials();
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const dim3 grid = WaveGrid(NumBlocks(count * DtypeSize(dt), kListTileBytes));
+    DispatchListDtype(dt, [&](auto* elem) {
+        using T = std::remove_pointer_t<decltype(elem)>;
+        SumSqKernel<T, LIST><<<grid, dim3(kBlock), 0, stream>>>(
+            reinterpret_cast<const T* const*>(seg_ptrs), tab, static_cast<const T*>(in), count,
+            partials);
+    });
+    HIP_CHECK(hipGetLastError());
+    SumSqFinishKernel<<<dim3(1), dim3(kBlock), 0, stream>>>(partials, static_cast<int>(grid.x),
+                                                            out, accumulate);
+    HIP_CHECK(hipGetLastError());
+}
+
+template <bool LIST>
+void LaunchClipScaleAny(void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg, void* data,
+                        size_t count, DataType dt, const double* total, float max_norm,
+                        hipStream_t stream, const char* where) {
+    CheckClipArgs<LIST>(seg_ptrs, seg_offs, nseg, data, count, dt, total, where);
+    const SegTable tab{seg_offs, static_cast<uint32_t>(nseg)};
+    const dim3 grid = WaveGrid(NumBlocks(count * DtypeSize(dt), kListTileBytes));
+    DispatchListDtype(dt, [&](auto* elem) {
+        using T = std::remove_pointer_t<decltype(elem)>;
+        ClipScaleKernel<T, LIST><<<grid, dim3(kBlock), 0, stream>>>(
+            reinterpret_cast<T* const*>(seg_ptrs), tab, static_cast<T*>(data), count, total,
+            max_norm);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+void LaunchSumSq(const void* in, size_t count, DataType dt, double* out, bool accumulate,
+                 hipStream_t stream) {
+    LaunchSumSqAny<false>(nullptr, nullptr, 0, in, count, dt, out, accumulate, stream, "sumsq");
+}
+
+void LaunchSumSqList(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                     size_t count, DataType dt, double* out, bool accumulate,
+                     hipStream_t stream) {
+    LaunchSumSqAny<true>(seg_ptrs, seg_offs, nseg, nullptr, count, dt, out, accumulate, stream,
+                         "sumsq-list");
+}
+
+void LaunchClipScale(void* data, size_t count, DataType dt, const double* total, float max_norm,
+                     hipStream_t stream) {
+    LaunchClipScaleAny<false>(nullptr, nullptr, 0, data, count, dt, total, max_norm, stream,
+                              "clip-scale");
+}
+
+void LaunchClipScaleList(void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                         size_t count, DataType dt, const double* total, float max_norm,
+                         hipStream_t stream) {
+    LaunchClipScaleAny<true>(seg_ptrs, seg_offs, nseg, nullptr, count, dt, total, max_norm,
+                             stream, "clip-scale-list");
 }
 
 // --- IPC p2p transport (comm/p2p_transport.cpp) ---

@@ -259,6 +259,36 @@ inline size_t ListElemsPerTrip(DataType dt) {
     return kListWavesPerTrip * (kListTileBytes / DtypeSize(dt));
 }
 
+// --- clipping by the global L2 norm, f32/bf16/f16 (anything else throws
+//     "supports f32/bf16/f16 only") ---
+// *out = (accumulate ? *out : 0) + the sum of v * v over the count >= 1
+// elements at `in`, every element converted to double and squared and added in
+// double; no atomics, so the same input at the same address modulo 16 gives the
+// same bits on every run. `out` is an 8-byte aligned double in DEVICE memory;
+// `in` needs its element's alignment only and is read with plain loads. The
+// list form is the same value for the concatenation V of the tensors (the
+// device tables of LaunchGatherList), in one launch and without building V.
+// Both run on the tile grid of the exact list kernels (ListElemsPerTrip holds)
+// and finish with a second launch of one workgroup over a partials buffer the
+// library keeps per device: two of these launches must not run at once on
+// different streams of one device.
+void LaunchSumSq(const void* in, size_t count, DataType dt, double* out, bool accumulate,
+                 hipStream_t stream);
+void LaunchSumSqList(const void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                     size_t count, DataType dt, double* out, bool accumulate,
+                     hipStream_t stream);
+// Every element becomes Encode(Decode(x) * factor), one float32 product rounded
+// once into the element type, with factor = (float)min(1.0, (double)max_norm /
+// (sqrt(*total) + 1e-6)) computed by the kernel from the double at `total` in
+// DEVICE memory: *total == 0 gives 1, an infinite or NaN total propagates by
+// arithmetic. Plain stores; no byte outside the count elements, or outside the
+// tensors, is written. Same tables and grid as above.
+void LaunchClipScale(void* data, size_t count, DataType dt, const double* total,
+                     float max_norm, hipStream_t stream);
+void LaunchClipScaleList(void* const* seg_ptrs, const uint64_t* seg_offs, size_t nseg,
+                         size_t count, DataType dt, const double* total, float max_norm,
+                         hipStream_t stream);
+
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,
 // the consumer does the copy — tests/examples/mlsl_test/mlsl_test.cpp:214-254.

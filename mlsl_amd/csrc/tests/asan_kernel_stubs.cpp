@@ -111,6 +111,10 @@ void LaunchDequantizeScatter4(const void* w, void* const* ptrs, const uint64_t* 
 void LaunchDequantizeSegments4(const void* w, size_t nseg, void* out, size_t n, size_t blk, DataType dt, bool acc, hipStream_t st, Quant4Path path) STUB(LaunchDequantizeSegments4, w, nseg, out, n, blk, dt, acc, st, path)
 void LaunchGatherList(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* flat, size_t n, DataType dt, hipStream_t st) STUB(LaunchGatherList, ptrs, offs, nseg, flat, n, dt, st)
 void LaunchScatterScaleList(const void* flat, void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, DataType dt, float post, hipStream_t st) STUB(LaunchScatterScaleList, flat, ptrs, offs, nseg, n, dt, post, st)
+void LaunchSumSq(const void* in, size_t n, DataType dt, double* out, bool acc, hipStream_t st) STUB(LaunchSumSq, in, n, dt, out, acc, st)
+void LaunchSumSqList(const void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, DataType dt, double* out, bool acc, hipStream_t st) STUB(LaunchSumSqList, ptrs, offs, nseg, n, dt, out, acc, st)
+void LaunchClipScale(void* data, size_t n, DataType dt, const double* total, float max_norm, hipStream_t st) STUB(LaunchClipScale, data, n, dt, total, max_norm, st)
+void LaunchClipScaleList(void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, DataType dt, const double* total, float max_norm, hipStream_t st) STUB(LaunchClipScaleList, ptrs, offs, nseg, n, dt, total, max_norm, st)
 void LaunchPack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchPack, s, d, pd, dt, st)
 void LaunchUnpack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchUnpack, s, d, pd, dt, st)
 void LaunchWaitFlag(const void* mbox, uint64_t target, const void* abort_word, void* status, uint64_t max_ticks, hipStream_t st) STUB(LaunchWaitFlag, mbox, target, abort_word, status, max_ticks, st)

@@ -120,6 +120,22 @@ def _lib():
                   "mlsl_hip_gather_list_tables", "mlsl_hip_scatter_scale_list_tables",
                   "mlsl_hip_list_elems_per_trip"):
             getattr(L, n).restype = c.c_int
+        L.mlsl_hip_sumsq.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_void_p, c.c_int]
+        L.mlsl_hip_sumsq_list.argtypes = [c.POINTER(c.c_void_p), c.POINTER(c.c_size_t),
+                                          c.c_size_t, c.c_int, c.c_void_p, c.c_int]
+        L.mlsl_hip_sumsq_list_tables.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t,
+                                                 c.c_size_t, c.c_int, c.c_void_p, c.c_int]
+        L.mlsl_hip_clip_scale.argtypes = [c.c_void_p, c.c_size_t, c.c_int, c.c_void_p,
+                                          c.c_float]
+        L.mlsl_hip_clip_scale_list.argtypes = [c.POINTER(c.c_void_p), c.POINTER(c.c_size_t),
+                                               c.c_size_t, c.c_int, c.c_void_p, c.c_float]
+        L.mlsl_hip_clip_scale_list_tables.argtypes = [c.c_void_p, c.c_void_p, c.c_size_t,
+                                                      c.c_size_t, c.c_int, c.c_void_p,
+                                                      c.c_float]
+        for n in ("mlsl_hip_sumsq", "mlsl_hip_sumsq_list", "mlsl_hip_sumsq_list_tables",
+                  "mlsl_hip_clip_scale", "mlsl_hip_clip_scale_list",
+                  "mlsl_hip_clip_scale_list_tables"):
+            getattr(L, n).restype = c.c_int
         L.mlsl_hip_quantize_gather_tables.restype = c.c_int
         L.mlsl_hip_dequantize_scatter_tables.restype = c.c_int
         L.mlsl_hip_quantize_gather_shards.argtypes = [c.POINTER(c.c_void_p),
@@ -656,11 +672,80 @@ def scatter_scale_list_tables(flat, dev_ptrs, dev_offs, nseg, count, dtype="f32"
 
 
 def list_elems_per_trip(dtype):
-    """Elements one launch of `gather_list` or `scatter_scale_list` covers
-    before its grid-stride loop takes a second trip."""
+    """Elements one launch of `gather_list`, `scatter_scale_list`, `sumsq`,
+    `sumsq_list`, `clip_scale` or `clip_scale_list` covers before its
+    grid-stride loop takes a second trip."""
     n = ctypes.c_size_t(0)
     check(_lib().mlsl_hip_list_elems_per_trip(DTYPE[dtype], ctypes.byref(n)))
     return n.value
+
+
+def _f64_scalar(t, what):
+    """Pointer of the device f64 scalar `t`: a 1-element torch.float64 tensor or
+    a raw pointer."""
+    p, dt = _as_ptr_dtype(t)
+    if dt is not None and (dt != "f64" or t.numel() != 1):
+        raise ValueError(f"{what} must be one float64 element in device memory, not "
+                         f"{t.numel()} of {t.dtype}")
+    return p
+
+
+def sumsq(inp, count, out, dtype=None, accumulate=False):
+    """out = (out if accumulate else 0) + the sum of the squares of the first
+    `count` elements of `inp` (f32, bf16 or f16), every element converted to
+    float64 first and everything added in float64. `out` is a device f64
+    scalar: a 1-element torch.float64 tensor or a raw pointer; it is never read
+    back here. No atomics: the same input at the same address modulo 16 gives
+    the same bits every time."""
+    ip, d1 = _as_ptr_dtype(inp)
+    check(_lib().mlsl_hip_sumsq(ip, count, DTYPE[dtype or d1], _f64_scalar(out, "out"),
+                                1 if accumulate else 0))
+
+
+def sumsq_list(tensors, counts, out, dtype=None, accumulate=False):
+    """`sumsq` of the concatenation of `tensors` (counts[j] elements each) in
+    one launch, without building it. The segment tables are uploaded here, once
+    per call."""
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    check(_lib().mlsl_hip_sumsq_list(ptrs, cnts, nseg, DTYPE[dt], _f64_scalar(out, "out"),
+                                     1 if accumulate else 0))
+
+
+def sumsq_list_tables(dev_ptrs, dev_offs, nseg, count, out, dtype="f32", accumulate=False):
+    """`sumsq_list` over tables in DEVICE memory; see `quantize_gather_tables`."""
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    op_, _ = _as_ptr_dtype(dev_offs)
+    check(_lib().mlsl_hip_sumsq_list_tables(pp, op_, nseg, count, DTYPE[dtype],
+                                            _f64_scalar(out, "out"), 1 if accumulate else 0))
+
+
+def clip_scale(data, count, total, max_norm, dtype=None):
+    """Gradient clipping's scale, in place: the first `count` elements of `data`
+    times float32(min(1, max_norm / (sqrt(total) + 1e-6))), torch's coefficient,
+    one float32 product rounded once into the element type. `total`, the squared
+    norm, is a device f64 scalar as `sumsq` leaves it; the kernel reads it, the
+    host does not. max_norm is taken as a float32."""
+    dp, d1 = _as_ptr_dtype(data)
+    check(_lib().mlsl_hip_clip_scale(dp, count, DTYPE[dtype or d1],
+                                     _f64_scalar(total, "total"), max_norm))
+
+
+def clip_scale_list(tensors, counts, total, max_norm, dtype=None):
+    """`clip_scale` of every tensor of the list in one launch; nothing outside
+    the tensors is written. The segment tables are uploaded here, once per
+    call."""
+    ptrs, cnts, nseg, _, dt = _seg_tables(tensors, counts, dtype)
+    check(_lib().mlsl_hip_clip_scale_list(ptrs, cnts, nseg, DTYPE[dt],
+                                          _f64_scalar(total, "total"), max_norm))
+
+
+def clip_scale_list_tables(dev_ptrs, dev_offs, nseg, count, total, max_norm, dtype="f32"):
+    """`clip_scale_list` over tables in DEVICE memory; see
+    `quantize_gather_tables`."""
+    pp, _ = _as_ptr_dtype(dev_ptrs)
+    op_, _ = _as_ptr_dtype(dev_offs)
+    check(_lib().mlsl_hip_clip_scale_list_tables(pp, op_, nseg, count, DTYPE[dtype],
+                                                 _f64_scalar(total, "total"), max_norm))
 
 
 _ELEM_BYTES = {"f32": 4, "bf16": 2}

@@ -43,6 +43,7 @@ times float32(1/world), where the default path divides by world.
 import torch
 
 import mlsl_amd as mx
+from mlsl_amd import ops
 
 
 class DistributedData:
@@ -126,6 +127,12 @@ class DistributedData:
                         self.dist, [q.numel() for q in ps], dtype=_dt(ps[0]), group=group,
                         compression=None, post_scale=1.0 / self.world if average else 1.0)
 
+        # clip_grad_norm_: the squared norm on the device, and per dtype the
+        # device segment tables of the gradients with the addresses they hold
+        self._clip_total = None
+        self._clip_tables = {}
+        self.clip_table_uploads = 0
+
         for p in self._params:
             p.register_post_accumulate_grad_hook(self._hook)
         self._reset_counts()
@@ -186,6 +193,69 @@ class DistributedData:
             self._reqs[bi] = None
             self._flat[bi] = None
         self._reset_counts()
+
+    def clip_grad_norm_(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_ (L2) for the wrapped module, called
+        after finish_gradients(): the reduced gradients are the same on every
+        rank, so nothing is exchanged. On the device the gradients are grouped
+        by dtype (f32, bf16, f16) and each group is one launch over a segment
+        table: ops.sumsq_list adds every group's squares into one float64 scalar,
+        ops.clip_scale_list scales each group by min(1, max_norm / (norm +
+        1e-6)) read from that scalar. A group's device tables are kept and
+        uploaded again only when a gradient's address has changed. Returns the
+        norm before clipping as a 0-dim float64 tensor on the gradients' device;
+        nothing is read back. Gradients must be contiguous. CPU gradients take
+        the same steps as torch operations in float64."""
+        max_norm = float(max_norm)
+        if not (0.0 < max_norm < float("inf")):
+            raise ValueError(f"max_norm={max_norm!r}: expected a positive finite number")
+        groups = {}
+        for p in self._params:
+            g = p.grad
+            if g is None or g.numel() == 0:
+                continue
+            if not g.is_contiguous():
+                raise ValueError(
+                    f"clip_grad_norm_ scales gradients in place and needs them contiguous: "
+                    f"the gradient of a parameter of shape {tuple(p.shape)} has strides "
+                    f"{g.stride()}")
+            groups.setdefault(g.dtype, []).append(g)
+        if not groups:
+            return torch.zeros((), dtype=torch.float64)
+        first = next(iter(groups.values()))[0]
+        if not first.is_cuda:
+            total = sum(g.double().square().sum() for gs in groups.values() for g in gs)
+            factor = torch.clamp(max_norm / (total.sqrt() + 1e-6), max=1.0).to(torch.float32)
+            for gs in groups.values():
+                for g in gs:
+                    g.mul_(factor)
+            return total.sqrt()
+        if self._clip_total is None:
+            self._clip_total = torch.zeros(1, dtype=torch.float64, device=first.device)
+        tabs = [(_dt(gs[0]), self._clip_table(dt, gs)) for dt, gs in groups.items()]
+        for i, (dt, (ptrs, offs, nseg, count)) in enumerate(tabs):
+            ops.sumsq_list_tables(ptrs, offs, nseg, count, self._clip_total, dtype=dt,
+                                  accumulate=i > 0)
+        for dt, (ptrs, offs, nseg, count) in tabs:
+            ops.clip_scale_list_tables(ptrs, offs, nseg, count, self._clip_total, max_norm,
+                                       dtype=dt)
+        return self._clip_total.sqrt().reshape(())
+
+    def _clip_table(self, dtype, grads):
+        """(device pointers, device prefix offsets, nseg, count) of one dtype's
+        gradients, from the cache while their addresses and sizes are the same."""
+        key = tuple((g.data_ptr(), g.numel()) for g in grads)
+        hit = self._clip_tables.get(dtype)
+        if hit is None or hit[0] != key:
+            offs = [0]
+            for _, n in key:
+                offs.append(offs[-1] + n)
+            dev = grads[0].device
+            hit = (key, (torch.tensor([a for a, _ in key], dtype=torch.int64, device=dev),
+                         torch.tensor(offs, dtype=torch.int64, device=dev), len(key), offs[-1]))
+            self._clip_tables[dtype] = hit
+            self.clip_table_uploads += 1
+        return hit[1]
 
     def close(self):
         """Destroy the buckets' list requests, compressed or exact (none in

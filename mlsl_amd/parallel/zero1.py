@@ -39,6 +39,7 @@ with ``compression="int4", grads="in_place", rs_algo="direct"``.
 import torch
 
 import mlsl_amd as mx
+from mlsl_amd import ops
 
 
 def _dt(t):
@@ -83,7 +84,7 @@ class ShardedOptimizer:
 
     def __init__(self, params, opt_cls, dist=None, group="data",
                  reduce="none", average=True, compression="none", rs_algo=None,
-                 ag_compression="none", grads="copy", **opt_kwargs):
+                 ag_compression="none", grads="copy", max_grad_norm=None, **opt_kwargs):
         """reduce: "none" (grads already reduced, e.g. by DistributedData)
         or "rs" (this wrapper reduce-scatters raw local grads itself).
         compression: "none", or "int8" for the quantized reduce_scatter
@@ -118,7 +119,28 @@ class ShardedOptimizer:
         ``own_grad``, a tensor of its own. The parameters' bits are those of
         "copy". A parameter without a gradient counts as zeros (one cached
         zeros_like per such parameter) and a non-contiguous gradient goes
-        through .contiguous(). On a group of one nothing changes."""
+        through .contiguous(). On a group of one nothing changes.
+        max_grad_norm: None, or a positive finite number: step() clips the
+        reduced (and averaged) gradient by its global L2 norm before the
+        optimizer sees it, with torch.nn.utils.clip_grad_norm_'s coefficient
+        min(1, max_grad_norm / (norm + 1e-6)). Under reduce="rs" no rank holds
+        the reduced gradient, so clipping p.grad from outside would clip the
+        local, unreduced one; here every rank sums the squares of its own_grad
+        shard in float64 on the device (padding is zeros and adds nothing), one
+        exact f64 all_reduce of that scalar gives every rank the squared norm,
+        and each rank scales its own shard. Nothing is read back: ``grad_norm``
+        is a device tensor, the norm before clipping. From three ranks on the
+        f64 all_reduce may add in a different order on each rank, so the ranks'
+        norms can differ in the last bit; each rank scales only its own shard
+        and the parameters travel by all_gather, so the replicas still agree
+        bit for bit. Parameters must be f32, bf16 or f16. CPU tensors take the
+        same three steps as torch operations in float64."""
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (0.0 < max_grad_norm < float("inf")):
+                raise ValueError(f"max_grad_norm={max_grad_norm!r}: expected None or a "
+                                 "positive finite number")
+        self.max_grad_norm = max_grad_norm
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
         self.dist = dist or mx.Distribution(mx.world_size(), 1)
@@ -175,6 +197,12 @@ class ShardedOptimizer:
         if ag_compression != "none" and dt not in (torch.float32, torch.bfloat16):
             raise ValueError(f'ag_compression="{ag_compression}" supports f32/bf16 '
                              f'parameters, not {dt}')
+        if max_grad_norm is not None and dt not in (torch.float32, torch.bfloat16,
+                                                    torch.float16):
+            raise ValueError(f"max_grad_norm= supports f32/bf16/f16 parameters, not {dt}")
+        # the squared norm of the reduced gradient, on the device (max_grad_norm)
+        self._norm2 = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.grad_norm = None
         total = sum(p.numel() for p in self.params)
         # pad so the shard divides evenly (owned = ceil math in the
         # reference, mlsl_impl.cpp:401-411; padding is the flat analog)
@@ -285,6 +313,8 @@ class ShardedOptimizer:
             self._gather_grads()
             self.own_grad.copy_(self.flat_grad[:self.shard])
 
+        if self.max_grad_norm is not None:
+            self._clip_own_grad()
         self._shard_holder.grad = self.own_grad
         self.opt.step()
         self._shard_holder.grad = None
@@ -301,6 +331,26 @@ class ShardedOptimizer:
             mx.wait(self.dist.all_gather(self.own_param, self.shard,
                                          self.flat, dtype=_dt(self.flat),
                                          group=self.group))
+
+    def _clip_own_grad(self):
+        """own_grad, final and averaged, scaled by the clip coefficient of the
+        whole reduced gradient: shard sum of squares, one scalar all_reduce,
+        scale. The shards partition the padded gradient, so their sums add up
+        to the full squared norm under reduce="none" as under "rs"."""
+        g = self.own_grad
+        if g.is_cuda:
+            ops.sumsq(g, self.shard, self._norm2, dtype=_dt(g))
+        else:
+            self._norm2.copy_(g.double().square().sum())
+        if self.world > 1:
+            mx.wait(self.dist.all_reduce(self._norm2, self._norm2, 1, op="sum", dtype="f64",
+                                         group=self.group))
+        if g.is_cuda:
+            ops.clip_scale(g, self.shard, self._norm2, self.max_grad_norm, dtype=_dt(g))
+        else:
+            g.mul_(torch.clamp(self.max_grad_norm / (self._norm2.sqrt() + 1e-6),
+                               max=1.0).to(torch.float32))
+        self.grad_norm = self._norm2.sqrt()
 
     def zero_grad(self, set_to_none=False):
         for p in self.params:
