@@ -4,6 +4,7 @@
 // internally.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -498,6 +499,36 @@ int mlsl_hip_clip_scale_list_tables(void* const* dev_ptrs, const uint64_t* dev_o
     OPS_TRY LaunchClipScaleList(dev_ptrs, dev_offs, nseg, count, static_cast<DataType>(dt),
                                 total, max_norm, nullptr);
     SyncNullStream();
+    OPS_CATCH
+}
+
+// The fused AdamW step. `scalars` is the ten floats of AdamWScalars in its
+// order; `total` (may be null) is one double, in DEVICE memory for the device
+// form and in host memory for the host twin.
+int mlsl_hip_adamw_step(const void* g, void* p, void* m, void* v, void* out,
+                        const void* replica, size_t count, int dt, const double* total,
+                        const float* scalars, int path) {
+    OPS_TRY AdamWScalars s;
+    std::memcpy(&s, scalars, sizeof s);
+    LaunchAdamWStep(g, static_cast<float*>(p), static_cast<float*>(m), static_cast<float*>(v),
+                    out, replica, count, static_cast<DataType>(dt), total, s, nullptr,
+                    static_cast<Quant4Path>(path));
+    SyncNullStream();
+    OPS_CATCH
+}
+
+int mlsl_host_adamw_step(const void* g, void* p, void* m, void* v, void* out,
+                         const void* replica, size_t count, int dt, const double* total,
+                         const float* scalars) {
+    OPS_TRY AdamWScalars s;
+    std::memcpy(&s, scalars, sizeof s);
+    HostAdamWStep(g, static_cast<float*>(p), static_cast<float*>(m), static_cast<float*>(v), out,
+                  replica, count, static_cast<DataType>(dt), total, s);
+    OPS_CATCH
+}
+
+int mlsl_hip_adamw_elems_per_trip(size_t* out) {
+    OPS_TRY* out = AdamWElemsPerTrip();
     OPS_CATCH
 }
 

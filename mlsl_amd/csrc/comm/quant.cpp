@@ -545,6 +545,50 @@ void HostScatterScaleList(const void* flat, void* const* seg_ptrs, const uint64_
     }
 }
 
+void HostAdamWStep(const void* g, float* p, float* m, float* v, void* out, const void* replica,
+                   size_t count, DataType dt, const double* total, const AdamWScalars& s) {
+// every operation below rounds on its own, as the kernel's do
+#pragma clang fp contract(off)
+    if (dt != DataType::F32 && dt != DataType::BF16 && dt != DataType::F16)
+        MLSL_THROW("adamw-step supports f32/bf16/f16 only");
+    MLSL_CHECK(count >= 1, "adamw-step takes at least one element");
+    MLSL_CHECK(g != nullptr && p != nullptr && m != nullptr && v != nullptr,
+               "adamw-step: null gradient or state");
+    MLSL_CHECK(replica == nullptr || out != nullptr, "adamw-step: replica needs out");
+    // an element of g's type at index i, as a float and back; memcpy: any alignment
+    const auto load = [dt](const void* buf, size_t i) {
+        float f;
+        uint16_t h;
+        if (dt == DataType::F32) {
+            std::memcpy(&f, static_cast<const uint8_t*>(buf) + 4 * i, 4);
+            return f;
+        }
+        std::memcpy(&h, static_cast<const uint8_t*>(buf) + 2 * i, 2);
+        return dt == DataType::BF16 ? Bf16F(h) : F16F(h);
+    };
+    float coef = 1.0f;
+    if (total != nullptr) {
+        const double norm = std::sqrt(*total) * static_cast<double>(s.grad_scale);
+        const double r = static_cast<double>(s.max_norm) / (norm + 1e-6);
+        coef = static_cast<float>(r > 1.0 ? 1.0 : r);
+    }
+    for (size_t i = 0; i < count; ++i) {
+        const float gs = (load(g, i) * s.grad_scale) * coef;
+        m[i] = m[i] * s.b1 + gs * s.one_minus_b1;
+        v[i] = v[i] * s.b2 + (gs * gs) * s.one_minus_b2;
+        const float den = std::sqrt(v[i]) / s.bc2_sqrt + s.eps;
+        p[i] = p[i] * s.decay - (m[i] / den) * s.step_size;
+        if (out == nullptr) continue;
+        const float o = replica ? p[i] - load(replica, i) : p[i];
+        if (dt == DataType::F32) {
+            std::memcpy(static_cast<uint8_t*>(out) + 4 * i, &o, 4);
+        } else {
+            const uint16_t h = dt == DataType::BF16 ? F32BNan(o) : F32H(o);
+            std::memcpy(static_cast<uint8_t*>(out) + 2 * i, &h, 2);
+        }
+    }
+}
+
 const QuantPluginApi* LoadQuantPlugin(const QuantParams& qp) {
     if (qp.lib_path.empty()) return nullptr;
     static std::mutex mu;

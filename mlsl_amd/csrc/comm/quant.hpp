@@ -111,6 +111,12 @@ void HostGatherList(const void* const* seg_ptrs, const uint64_t* seg_offs, size_
 void HostScatterScaleList(const void* flat, void* const* seg_ptrs, const uint64_t* seg_offs,
                           size_t nseg, size_t count, DataType dt, float post_scale);
 
+// Host twin of LaunchAdamWStep (hip/kernels.hpp): the same sequence of float32
+// operations in plain loops, compiled without contraction, so the same bits;
+// every buffer at any alignment. `total` is read here, on the host.
+void HostAdamWStep(const void* g, float* p, float* m, float* v, void* out, const void* replica,
+                   size_t count, DataType dt, const double* total, const AdamWScalars& s);
+
 // dlopen'd compression plugin (reference quant/quant.c ABI — Intel
 // DL-comp style). Loaded once per lib_path; used by the HOST compressed
 // path when QuantParams.lib_path is set. Signatures quant/quant.c:57-65.

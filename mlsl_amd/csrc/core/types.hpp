@@ -134,6 +134,15 @@ struct QuantParams {
     }
 };
 
+// The float32 scalars of one fused AdamW step (LaunchAdamWStep in
+// hip/kernels.hpp, HostAdamWStep in comm/quant.hpp). The caller computes them
+// in double and rounds each once: step_size = lr / (1 - b1^t), bc2_sqrt =
+// sqrt(1 - b2^t), decay = 1 - lr * weight_decay.
+struct AdamWScalars {
+    float grad_scale, max_norm, b1, b2, one_minus_b1, one_minus_b2, step_size, bc2_sqrt, eps,
+        decay;
+};
+
 class Error : public std::runtime_error {
   public:
     explicit Error(const std::string& what) : std::runtime_error(what) {}

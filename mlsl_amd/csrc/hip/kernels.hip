@@ -3553,6 +3553,212 @@ void LaunchClipScaleList(void* const* seg_ptrs, const uint64_t* seg_offs, size_t
                              stream, "clip-scale-list");
 }
 
+// ---------------------------------------------------------------------------
+// Fused AdamW step on a flat shard with f32 master weights: averaging, the clip
+// coefficient, both moments, the decoupled decay, the update and the rounded
+// parameter (or its delta to the replica) in one pass. kernels.hpp pins the
+// arithmetic; this is how the bytes move.
+//
+// 24 of the 28 bytes an element moves in each direction (16-bit gradients) are
+// the three f32 states, which are always 16-byte aligned, so the work is split
+// on their 16-byte vectors: a "quad" is 4 consecutive elements, one float4 of
+// p, m and v each. A wave owns a tile of kAdamWQuadsPerWave = 128 quads and
+// grid-strides over tiles on the list kernels' bounded grid (WaveGrid); inside a
+// tile lane l takes quads l and l + 64, so every load and store instruction of
+// the wave covers one contiguous span: 1 KiB of a state, 512 bytes of a 16-bit
+// gradient. (Eight consecutive elements a lane, one 16-byte gradient load,
+// would stride the six state loads by 32 bytes and touch every line twice.)
+// All of a lane's loads, six state vectors, two gradient quads and with a
+// replica two more, are issued before the first use; 2048 workgroups of four
+// waves keep 3 KiB of state a wave in flight, more than HBM's latency needs.
+//
+// The gradient, `out` and `replica` are views at rank * shard elements into a
+// flat buffer, so an odd shard leaves them off 16 bytes while the states stay
+// aligned. ALIGNED (all three 16-byte aligned) moves a quad of them as one 8-
+// or 16-byte vector; otherwise the same lane moves the same quad element by
+// element, the states still as vectors. The count % 4 elements after the last
+// whole quad, where a state vector would run past the buffer, are done one
+// element each by the first lanes of the grid's first wave.
+//
+// `out` is read next by an all-gather, possibly from another device, and
+// without `out` (f32 parameters stepping where they lie) `p` itself is: both
+// always take plain loads and stores (docs/STATUS.md on nontemporal stores and
+// hand-offs). `m` and `v` are this kernel's alone, read and written once a step.
+// Up to kAdamWCachedStateBytes of state they are still cached when the next
+// step comes and plain accesses win; past it NT_MOMENTS moves the two of them
+// nontemporally. The measurements are in docs/BENCHMARKS.md.
+
+namespace {
+
+constexpr size_t kAdamWQuadsPerWave = 128;   // 64 lanes x 2 in flight
+constexpr size_t kAdamWCachedStateBytes = size_t(256) << 20;   // the MI355X's last-level cache
+
+template <typename T> struct alignas(4 * sizeof(T)) Quad { T e[4]; };
+
+template <typename T, bool ALIGNED>
+__device__ __forceinline__ Quad<T> LoadQuad(const T* src) {
+    Quad<T> q;
+    if constexpr (ALIGNED) {
+        q = *reinterpret_cast<const Quad<T>*>(src);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q.e[j] = src[j];
+    }
+    return q;
+}
+
+template <typename T, bool ALIGNED>
+__device__ __forceinline__ void StoreQuad(T* dst, const Quad<T>& q) {
+    if constexpr (ALIGNED) {
+        *reinterpret_cast<Quad<T>*>(dst) = q;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dst[j] = q.e[j];
+    }
+}
+
+// __fmul_rn and its kin are plain operators in this toolchain's default build
+// and __fsqrt_rn the native, one-ulp square root, so neither pins anything
+// here. What does: the pragma takes the `contract` flag off every operation of
+// the block, and without fast-math flags `/` and __builtin_sqrtf are the
+// correctly rounded expansions.
+__device__ __forceinline__ float AdamWCoef(const double* total, const AdamWScalars& s) {
+#pragma clang fp contract(off)
+    if (total == nullptr) return 1.0f;
+    const double norm = sqrt(*total) * static_cast<double>(s.grad_scale);
+    const double r = static_cast<double>(s.max_norm) / (norm + 1e-6);
+    return static_cast<float>(r > 1.0 ? 1.0 : r);
+}
+
+__device__ __forceinline__ void AdamWElem(float g, float coef, const AdamWScalars& s, float& p,
+                                          float& m, float& v) {
+#pragma clang fp contract(off)
+    const float gs = (g * s.grad_scale) * coef;
+    m = m * s.b1 + gs * s.one_minus_b1;
+    v = v * s.b2 + (gs * gs) * s.one_minus_b2;
+    const float den = __builtin_sqrtf(v) / s.bc2_sqrt + s.eps;
+    p = p * s.decay - (m / den) * s.step_size;
+}
+
+// What `out` takes for the new p: its rounding, or that of its distance to the
+// replica (one f32 subtraction).
+template <typename T>
+__device__ __forceinline__ T AdamWOut(float p, bool delta, T replica) {
+#pragma clang fp contract(off)
+    return Encode<T>(delta ? p - Decode(replica) : p);
+}
+
+template <bool NT>
+__device__ __forceinline__ float4_ev LoadState(const float4_ev* p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
+template <bool NT>
+__device__ __forceinline__ void StoreState(float4_ev* p, float4_ev x) {
+    if constexpr (NT) __builtin_nontemporal_store(x, p);
+    else *p = x;
+}
+
+template <typename T, bool ALIGNED, bool DELTA, bool NT_MOMENTS>
+__global__ void AdamWStepKernel(const T* __restrict__ g, float* __restrict__ p,
+                                float* __restrict__ m, float* __restrict__ v,
+                                T* __restrict__ out, const T* __restrict__ replica, size_t count,
+                                const double* __restrict__ total, AdamWScalars s) {
+    const float coef = AdamWCoef(total, s);
+    const size_t nquad = count / 4;
+    float4_ev* p4 = reinterpret_cast<float4_ev*>(p);
+    float4_ev* m4 = reinterpret_cast<float4_ev*>(m);
+    float4_ev* v4 = reinterpret_cast<float4_ev*>(v);
+    ForEachWaveBlock(
+        (nquad + kAdamWQuadsPerWave - 1) / kAdamWQuadsPerWave, [&](size_t tile, int lane) {
+            const size_t first = WaveUniform(tile) * kAdamWQuadsPerWave;
+            // `whole` is a compile-time true for every tile but the last: no
+            // branch then stands between the loads, and all are issued at once
+            const auto run = [&](auto whole) {
+                float4_ev pv[2], mv[2], vv[2];
+                Quad<T> gv[2], rv[2] = {};
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const size_t q = first + lane + 64 * k;
+                    if (decltype(whole)::value || q < nquad) {
+                        gv[k] = LoadQuad<T, ALIGNED>(g + 4 * q);
+                        pv[k] = p4[q];
+                        mv[k] = LoadState<NT_MOMENTS>(m4 + q);
+                        vv[k] = LoadState<NT_MOMENTS>(v4 + q);
+                        if constexpr (DELTA) rv[k] = LoadQuad<T, ALIGNED>(replica + 4 * q);
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const size_t q = first + lane + 64 * k;
+                    if (decltype(whole)::value || q < nquad) {
+                        Quad<T> ov;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            float pj = pv[k][j], mj = mv[k][j], vj = vv[k][j];
+                            AdamWElem(Decode(gv[k].e[j]), coef, s, pj, mj, vj);
+                            pv[k][j] = pj, mv[k][j] = mj, vv[k][j] = vj;
+                            ov.e[j] = AdamWOut<T>(pj, DELTA, rv[k].e[j]);
+                        }
+                        p4[q] = pv[k];
+                        StoreState<NT_MOMENTS>(m4 + q, mv[k]);
+                        StoreState<NT_MOMENTS>(v4 + q, vv[k]);
+                        if (out) StoreQuad<T, ALIGNED>(out + 4 * q, ov);
+                    }
+                }
+            };
+            if (first + kAdamWQuadsPerWave <= nquad) run(std::true_type{});
+            else run(std::false_type{});
+        });
+    const size_t i = nquad * 4 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) {
+        AdamWElem(Decode(g[i]), coef, s, p[i], m[i], v[i]);
+        if (out) out[i] = AdamWOut<T>(p[i], DELTA, DELTA ? replica[i] : T{});
+    }
+}
+
+}  // namespace
+
+size_t AdamWElemsPerTrip() { return kListWavesPerTrip * kAdamWQuadsPerWave * 4; }
+
+void LaunchAdamWStep(const void* g, float* p, float* m, float* v, void* out,
+                     const void* replica, size_t count, DataType dt, const double* total,
+                     const AdamWScalars& s, hipStream_t stream, Quant4Path path) {
+    if (dt != DataType::F32 && dt != DataType::BF16 && dt != DataType::F16)
+        MLSL_THROW("adamw-step supports f32/bf16/f16 only");
+    MLSL_CHECK(count >= 1, "adamw-step takes at least one element");
+    const auto addr = [](const void* x) { return reinterpret_cast<uintptr_t>(x); };
+    MLSL_CHECK(p != nullptr && m != nullptr && v != nullptr &&
+                   ((addr(p) | addr(m) | addr(v)) & 15) == 0,
+               "adamw-step: p, m and v must be 16-byte aligned f32 buffers");
+    MLSL_CHECK(replica == nullptr || out != nullptr, "adamw-step: replica needs out");
+    MLSL_CHECK(g != nullptr && ((addr(g) | addr(out) | addr(replica)) & (DtypeSize(dt) - 1)) == 0,
+               "adamw-step: g, out and replica must be aligned to their element");
+    MLSL_CHECK(total == nullptr || (addr(total) & 7) == 0,
+               "adamw-step: total must be 8-byte aligned device memory");
+    const bool fits = ((addr(g) | addr(out) | addr(replica)) & 15) == 0;
+    if (path == Quant4Path::FAST)
+        MLSL_CHECK(fits, "adamw-step: the fast path needs g, out and replica 16-byte aligned");
+    const bool fast = path != Quant4Path::GENERIC && fits;
+    const bool nt = count * 3 * sizeof(float) > kAdamWCachedStateBytes;
+    const dim3 grid = WaveGrid(NumBlocks(count, 4 * kAdamWQuadsPerWave));
+    DispatchListDtype(dt, [&](auto* elem) {
+        using T = std::remove_pointer_t<decltype(elem)>;
+        DispatchBool(fast, [&](auto aligned) {
+            DispatchBool(replica != nullptr, [&](auto delta) {
+                DispatchBool(nt, [&](auto nts) {
+                    AdamWStepKernel<T, decltype(aligned)::value, decltype(delta)::value,
+                                    decltype(nts)::value><<<grid, dim3(kBlock), 0, stream>>>(
+                        static_cast<const T*>(g), p, m, v, static_cast<T*>(out),
+                        static_cast<const T*>(replica), count, total, s);
+                });
+            });
+        });
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
 // --- IPC p2p transport (comm/p2p_transport.cpp) ---
 // Mailboxes are monotonically increasing u64 sequence counters in the
 // receiver's HBM window; the writer is a remote process on the same or a

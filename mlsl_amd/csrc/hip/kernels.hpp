@@ -289,6 +289,35 @@ void LaunchClipScaleList(void* const* seg_ptrs, const uint64_t* seg_offs, size_t
                          size_t count, DataType dt, const double* total, float max_norm,
                          hipStream_t stream);
 
+// --- fused AdamW step on a flat shard with f32 master weights ---
+// For every i < count, each line one float32 operation rounded to nearest
+// even, never contracted into an fma:
+//   coef = total ? float(min(1.0, double(max_norm) /
+//                            (sqrt(*total) * double(grad_scale) + 1e-6))) : 1
+//   g'   = (float(g[i]) * grad_scale) * coef
+//   m[i] = m[i] * b1 + g' * one_minus_b1
+//   v[i] = v[i] * b2 + (g' * g') * one_minus_b2
+//   den  = sqrt(v[i]) / bc2_sqrt + eps
+//   p[i] = p[i] * decay - (m[i] / den) * step_size
+// coef is computed in double by every thread from the double at `total` in
+// DEVICE memory (the squared norm as LaunchSumSq leaves it); the host never
+// reads it. `g` is f32, bf16 or f16 (anything else throws "supports
+// f32/bf16/f16 only") and is only read. `p`, `m`, `v` are f32, 16-byte aligned
+// (checked) and updated in place. `out` (may be null) has g's type: without
+// `replica` out[i] = Encode(p[i]), with it out[i] = Encode(p[i] -
+// Decode(replica[i])), the new p; `replica` is only read and needs `out`.
+// `out` takes plain stores: a collective reads it next. `g`, `out` and
+// `replica` need their element's alignment only; when all of them are 16-byte
+// aligned the kernel moves them as vectors (Quant4Path::FAST, refused when they
+// are not), else element by element (GENERIC). No byte outside count elements
+// of any buffer is written. One launch covers AdamWElemsPerTrip() elements
+// before its grid-stride loop takes a second trip.
+size_t AdamWElemsPerTrip();
+void LaunchAdamWStep(const void* g, float* p, float* m, float* v, void* out,
+                     const void* replica, size_t count, DataType dt, const double* total,
+                     const AdamWScalars& s, hipStream_t stream,
+                     Quant4Path path = Quant4Path::AUTO);
+
 // Strided pack/unpack between layer layout [mb][fm][fmSize] and a contiguous
 // comm buffer block (CommBlockInfo contract; reference computes the shapes,
 // the consumer does the copy — tests/examples/mlsl_test/mlsl_test.cpp:214-254.

@@ -101,6 +101,7 @@ void LaunchQuantSumRequantN4(const void* const* w, int nw, void* dst, size_t uni
     for (int k = 0; k < nw; ++k) Record(" wire", w[k]);
 }
 size_t Quant4BlocksPerTrip(bool fast) { return fast ? 16384 : 8192; }
+size_t AdamWElemsPerTrip() { return kListWavesPerTrip * 512; }
 void LaunchDequantizeSegments(const void* w, size_t nseg, void* out, size_t n, size_t blk, DataType dt, bool acc, hipStream_t st) STUB(LaunchDequantizeSegments, w, nseg, out, n, blk, dt, acc, st)
 void LaunchQuantizeGather(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t n, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGather, ptrs, offs, nseg, err, w, n, blk, dt, use_err, st)
 void LaunchQuantizeGatherShards(const void* const* ptrs, const uint64_t* offs, size_t nseg, void* err, void* w, size_t total, size_t nshards, size_t shard, size_t stride, size_t blk, DataType dt, bool use_err, hipStream_t st) STUB(LaunchQuantizeGatherShards, ptrs, offs, nseg, err, w, total, nshards, shard, stride, blk, dt, use_err, st)
@@ -115,6 +116,7 @@ void LaunchSumSq(const void* in, size_t n, DataType dt, double* out, bool acc, h
 void LaunchSumSqList(const void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, DataType dt, double* out, bool acc, hipStream_t st) STUB(LaunchSumSqList, ptrs, offs, nseg, n, dt, out, acc, st)
 void LaunchClipScale(void* data, size_t n, DataType dt, const double* total, float max_norm, hipStream_t st) STUB(LaunchClipScale, data, n, dt, total, max_norm, st)
 void LaunchClipScaleList(void* const* ptrs, const uint64_t* offs, size_t nseg, size_t n, DataType dt, const double* total, float max_norm, hipStream_t st) STUB(LaunchClipScaleList, ptrs, offs, nseg, n, dt, total, max_norm, st)
+void LaunchAdamWStep(const void* g, float* p, float* m, float* v, void* out, const void* replica, size_t n, DataType dt, const double* total, const AdamWScalars& s, hipStream_t st, Quant4Path path) STUB(LaunchAdamWStep, g, p, m, v, out, replica, n, dt, total, &s, st, path)
 void LaunchPack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchPack, s, d, pd, dt, st)
 void LaunchUnpack(const void* s, void* d, const PackBlockDesc& pd, DataType dt, hipStream_t st) STUB(LaunchUnpack, s, d, pd, dt, st)
 void LaunchWaitFlag(const void* mbox, uint64_t target, const void* abort_word, void* status, uint64_t max_ticks, hipStream_t st) STUB(LaunchWaitFlag, mbox, target, abort_word, status, max_ticks, st)

@@ -8,6 +8,7 @@ Buffers: torch CUDA tensors, raw integer device pointers, or anything with
 csrc/comm/quant.cpp (same wire format) on numpy arrays.
 """
 import ctypes
+import math
 
 from .._lib import lib as _core_lib, check
 from ..api import DTYPE, REDOP, _as_ptr_dtype
@@ -135,6 +136,13 @@ def _lib():
         for n in ("mlsl_hip_sumsq", "mlsl_hip_sumsq_list", "mlsl_hip_sumsq_list_tables",
                   "mlsl_hip_clip_scale", "mlsl_hip_clip_scale_list",
                   "mlsl_hip_clip_scale_list_tables"):
+            getattr(L, n).restype = c.c_int
+        L.mlsl_hip_adamw_step.argtypes = [c.c_void_p] * 6 + [c.c_size_t, c.c_int, c.c_void_p,
+                                                              c.POINTER(c.c_float), c.c_int]
+        L.mlsl_host_adamw_step.argtypes = L.mlsl_hip_adamw_step.argtypes[:-1]
+        L.mlsl_hip_adamw_elems_per_trip.argtypes = [c.POINTER(c.c_size_t)]
+        for n in ("mlsl_hip_adamw_step", "mlsl_host_adamw_step",
+                  "mlsl_hip_adamw_elems_per_trip"):
             getattr(L, n).restype = c.c_int
         L.mlsl_hip_quantize_gather_tables.restype = c.c_int
         L.mlsl_hip_dequantize_scatter_tables.restype = c.c_int
@@ -746,6 +754,92 @@ def clip_scale_list_tables(dev_ptrs, dev_offs, nseg, count, total, max_norm, dty
     op_, _ = _as_ptr_dtype(dev_offs)
     check(_lib().mlsl_hip_clip_scale_list_tables(pp, op_, nseg, count, DTYPE[dtype],
                                                  _f64_scalar(total, "total"), max_norm))
+
+
+def _adamw_args(lr, betas, eps, weight_decay, step, grad_scale, total, max_norm, out, replica,
+                dtype):
+    """The refusals the device and the host form share, and the ten float32
+    scalars in AdamWScalars' order: each computed in double, rounded once."""
+    if int(step) < 1:
+        raise ValueError(f"step={step!r}: the bias corrections need a step count of at "
+                         "least 1")
+    if replica is not None and out is None:
+        raise ValueError("replica without out: the delta to the replica has nowhere to go")
+    if (total is None) != (max_norm is None):
+        raise ValueError("total and max_norm go together: the squared norm and its bound")
+    if dtype not in _LIST_ELEM_BYTES:
+        raise ValueError(f"gradient dtype {dtype!r}: adamw_step supports f32/bf16/f16 only")
+    b1, b2 = float(betas[0]), float(betas[1])
+    return (ctypes.c_float * 10)(
+        grad_scale, 0.0 if max_norm is None else max_norm, b1, b2, 1.0 - b1, 1.0 - b2,
+        lr / (1.0 - b1 ** step), math.sqrt(1.0 - b2 ** step), eps, 1.0 - lr * weight_decay)
+
+
+def adamw_elems_per_trip():
+    """Elements one launch of `adamw_step` covers before its grid-stride loop
+    takes a second trip (the same for every gradient dtype)."""
+    n = ctypes.c_size_t(0)
+    check(_lib().mlsl_hip_adamw_elems_per_trip(ctypes.byref(n)))
+    return n.value
+
+
+def adamw_step(grad, p, m, v, count, *, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01,
+               step, grad_scale=1.0, total=None, max_norm=None, out=None, replica=None,
+               dtype=None, path=None):
+    """One fused AdamW step over the first `count` elements of a flat shard,
+    in one pass and in float32 operations that each round once (no fma):
+
+        coef = min(1, max_norm / (sqrt(total) * grad_scale + 1e-6))  # 1 without total
+        g'   = (float(grad) * grad_scale) * coef
+        m    = m * b1 + g' * (1 - b1)
+        v    = v * b2 + (g' * g') * (1 - b2)
+        p    = p * (1 - lr * weight_decay)
+               - (m / (sqrt(v) / sqrt(1 - b2**step) + eps)) * (lr / (1 - b1**step))
+
+    `grad` is f32, bf16 or f16 and only read. `p`, `m`, `v` are float32,
+    16-byte aligned and updated in place: the master weights and both moments.
+    `total` is the unscaled squared norm as a device f64 scalar (`sumsq` leaves
+    it so); the kernel reads it, the host does not. `out`, in grad's dtype,
+    takes the rounded new p, or with `replica` (only read) the rounded
+    p - replica. path=None moves grad, out and replica as vectors when all are
+    16-byte aligned and element by element otherwise; "generic" and "fast" name
+    the path, and "fast" on misaligned buffers is refused."""
+    gp, d1 = _as_ptr_dtype(grad)
+    dt = dtype or d1
+    sc = _adamw_args(lr, betas, eps, weight_decay, step, grad_scale, total, max_norm, out,
+                     replica, dt)
+    state = []
+    for name, t in (("p", p), ("m", m), ("v", v)):
+        tp, td = _as_ptr_dtype(t)
+        if td not in (None, "f32") or tp.value is None or tp.value % 16:
+            raise ValueError(f"{name} must be a 16-byte aligned float32 buffer")
+        state.append(tp)
+    op_, _ = _as_ptr_dtype(out)
+    rp, _ = _as_ptr_dtype(replica)
+    check(_lib().mlsl_hip_adamw_step(gp, *state, op_, rp, count, DTYPE[dt],
+                                     None if total is None else _f64_scalar(total, "total"),
+                                     sc, _PATH4[path]))
+
+
+def host_adamw_step(grad, p, m, v, count, *, lr, betas=(0.9, 0.999), eps=1e-8,
+                    weight_decay=0.01, step, grad_scale=1.0, total=None, max_norm=None,
+                    out=None, replica=None, dtype="f32"):
+    """Host twin of `adamw_step` on numpy arrays: the same bits. bf16 and f16
+    travel as uint16 bit patterns; p, m and v are float32 arrays; `total` is a
+    Python float, the squared norm."""
+    sc = _adamw_args(lr, betas, eps, weight_decay, step, grad_scale, total, max_norm, out,
+                     replica, dtype)
+    for name, a in (("p", p), ("m", m), ("v", v)):
+        if str(getattr(a, "dtype", None)) != "float32":
+            raise ValueError(f"{name} must be a float32 array")
+    eb = _LIST_ELEM_BYTES[dtype]
+    tot = None if total is None else ctypes.byref(ctypes.c_double(total))
+    check(_lib().mlsl_host_adamw_step(
+        _host_buf(grad, count * eb, "grad"), _host_buf(p, count * 4, "p"),
+        _host_buf(m, count * 4, "m"), _host_buf(v, count * 4, "v"),
+        None if out is None else _host_buf(out, count * eb, "out"),
+        None if replica is None else _host_buf(replica, count * eb, "replica"),
+        count, DTYPE[dtype], tot, sc))
 
 
 _ELEM_BYTES = {"f32": 4, "bf16": 2}

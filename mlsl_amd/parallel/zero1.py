@@ -47,6 +47,12 @@ def _dt(t):
             torch.bfloat16: "bf16", torch.float16: "f16"}[t.dtype]
 
 
+def _np(t):
+    """A CPU tensor's memory as the numpy array the host kernels take: 16-bit
+    floats as their uint16 bit patterns."""
+    return (t if t.dtype == torch.float32 else t.view(torch.int16)).numpy()
+
+
 class ShardedOptimizer:
     """``ag_compression="int8"`` sends the updated shard back as int8 too.
 
@@ -80,6 +86,17 @@ class ShardedOptimizer:
     and one delta shard per rank. A group of one exchanges nothing and steps
     on ``flat`` as without it. A model checkpoint holds replica values; a
     newly constructed optimizer seeds ``master`` from them.
+
+    ``opt_cls="adamw"`` (a string in place of the optimizer class, with ``lr``,
+    ``betas``, ``eps``, ``weight_decay``) steps with this project's fused
+    kernel, ``ops.adamw_step``, instead of a torch optimizer. The owner keeps
+    ``master``, ``exp_avg`` and ``exp_avg_sq`` in float32 whatever the
+    parameter dtype, 12 bytes per owned element, and one launch does the
+    averaging, the clip's scaling, AdamW and the rounding of the new
+    parameter into ``flat`` (or, under ``ag_compression``, of ``master -
+    replica`` into the delta). ``lr`` is a plain attribute read at every
+    step. For f32 parameters without ``ag_compression`` ``master`` is the
+    owned slice of ``flat`` itself where that slice is 16-byte aligned.
     """
 
     def __init__(self, params, opt_cls, dist=None, group="data",
@@ -140,6 +157,10 @@ class ShardedOptimizer:
             if not (0.0 < max_grad_norm < float("inf")):
                 raise ValueError(f"max_grad_norm={max_grad_norm!r}: expected None or a "
                                  "positive finite number")
+        self._fused = isinstance(opt_cls, str)
+        if self._fused and opt_cls != "adamw":
+            raise ValueError(f"opt_cls={opt_cls!r}: the only built-in optimizer is 'adamw'; "
+                             "anything else is passed as a torch optimizer class")
         self.max_grad_norm = max_grad_norm
         self.params = [p for p in params if p.requires_grad]
         assert self.params, "no trainable parameters"
@@ -200,6 +221,8 @@ class ShardedOptimizer:
         if max_grad_norm is not None and dt not in (torch.float32, torch.bfloat16,
                                                     torch.float16):
             raise ValueError(f"max_grad_norm= supports f32/bf16/f16 parameters, not {dt}")
+        if self._fused and dt not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f'"adamw" supports f32/bf16/f16 parameters, not {dt}')
         # the squared norm of the reduced gradient, on the device (max_grad_norm)
         self._norm2 = torch.zeros(1, dtype=torch.float64, device=dev)
         self.grad_norm = None
@@ -233,11 +256,14 @@ class ShardedOptimizer:
                                              dtype=_dt(self.flat), group=group,
                                              quantized=True, accumulate=True,
                                              bits=4 if ag_compression == "int4" else 8)
-        # the wrapped optimizer sees ONLY the owned shard (state: 1/dp)
-        shard_param = torch.nn.Parameter(
-            self.own_param if self.master is None else self.master, requires_grad=False)
-        self._shard_holder = shard_param
-        self.opt = opt_cls([shard_param], **opt_kwargs)
+        if self._fused:
+            self._init_fused(**opt_kwargs)
+        else:
+            # the wrapped optimizer sees ONLY the owned shard (state: 1/dp)
+            shard_param = torch.nn.Parameter(
+                self.own_param if self.master is None else self.master, requires_grad=False)
+            self._shard_holder = shard_param
+            self.opt = opt_cls([shard_param], **opt_kwargs)
         # built once: the request owns the error-feedback residual
         self._qrs = None
         self._qrs_seg = None
@@ -252,6 +278,22 @@ class ShardedOptimizer:
                                              group=group, quantized=True,
                                              algo=rs_algo,
                                              bits=4 if compression == "int4" else 8)
+
+    def _init_fused(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        """State of the built-in AdamW: f32 master weights and moments of the
+        owned shard. f32 parameters that travel exactly step where they lie,
+        unless an odd shard leaves this rank's slice of flat off 16 bytes: the
+        kernel's states are vectors, so master is then a buffer of its own and
+        the slice takes the new parameter as `out`, the same bits."""
+        self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
+        self.step_count = 0
+        if (self.flat.dtype == torch.float32 and self._qag is None
+                and self.own_param.data_ptr() % 16 == 0):
+            self.master = self.own_param
+        else:
+            self.master = self.own_param.detach().to(torch.float32, copy=True)
+        self.exp_avg = torch.zeros_like(self.master)
+        self.exp_avg_sq = torch.zeros_like(self.master)
 
     def _grad_list(self):
         """The gradients as the list request reads them: contiguous, zeros
@@ -288,7 +330,7 @@ class ShardedOptimizer:
             self._qrs_seg.start(grads, self.own_grad)
             self._qrs_seg.wait()
             del grads
-            if self.average:
+            if self.average and not self._fused:
                 self.own_grad /= self.world
         elif self.world > 1:
             self._gather_grads()
@@ -307,22 +349,26 @@ class ShardedOptimizer:
                 self.own_grad.copy_(
                     self.flat_grad[self.rank * self.shard:
                                    (self.rank + 1) * self.shard])
-            if self.average and self.reduce == "rs":
+            if self.average and self.reduce == "rs" and not self._fused:
                 self.own_grad /= self.world
         else:
             self._gather_grads()
             self.own_grad.copy_(self.flat_grad[:self.shard])
 
-        if self.max_grad_norm is not None:
-            self._clip_own_grad()
-        self._shard_holder.grad = self.own_grad
-        self.opt.step()
-        self._shard_holder.grad = None
+        if self._fused:
+            self._fused_step()
+        else:
+            if self.max_grad_norm is not None:
+                self._clip_own_grad()
+            self._shard_holder.grad = self.own_grad
+            self.opt.step()
+            self._shard_holder.grad = None
 
         if self._qag is not None:
             # what the replica lacks, last step's rounding included, quantized;
             # every rank adds every segment the same way
-            torch.sub(self.master, self.own_param, out=self._delta)
+            if not self._fused:
+                torch.sub(self.master, self.own_param, out=self._delta)
             self._qag.start(self._delta, self.flat)
             self._qag.wait()
         elif self.world > 1:
@@ -332,11 +378,39 @@ class ShardedOptimizer:
                                          self.flat, dtype=_dt(self.flat),
                                          group=self.group))
 
-    def _clip_own_grad(self):
-        """own_grad, final and averaged, scaled by the clip coefficient of the
-        whole reduced gradient: shard sum of squares, one scalar all_reduce,
-        scale. The shards partition the padded gradient, so their sums add up
-        to the full squared norm under reduce="none" as under "rs"."""
+    def _fused_step(self):
+        """The built-in AdamW on the owned shard, one launch: own_grad is the
+        reduced SUM (the kernel averages by grad_scale), _norm2 its squared
+        norm, unscaled (the kernel clips from it). The rounded parameter goes
+        to own_param, or under ag_compression master - own_param to _delta."""
+        g = self.own_grad
+        scale = (float(torch.tensor(1.0 / self.world, dtype=torch.float32))
+                 if self.average and self.reduce == "rs" else 1.0)
+        clip = self.max_grad_norm is not None
+        if clip:
+            self._sum_squares()
+            self.grad_norm = self._norm2.sqrt() * scale
+        self.step_count += 1
+        kw = dict(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                  step=self.step_count, grad_scale=scale, dtype=_dt(g),
+                  max_norm=self.max_grad_norm)
+        if self._qag is not None:
+            out, replica = self._delta, self.own_param
+        else:
+            out, replica = (None if self.master is self.own_param else self.own_param), None
+        if g.is_cuda:
+            ops.adamw_step(g, self.master, self.exp_avg, self.exp_avg_sq, self.shard,
+                           total=self._norm2 if clip else None, out=out, replica=replica, **kw)
+        else:
+            ops.host_adamw_step(_np(g), _np(self.master), _np(self.exp_avg),
+                                _np(self.exp_avg_sq), self.shard,
+                                total=float(self._norm2) if clip else None,
+                                out=None if out is None else _np(out),
+                                replica=None if replica is None else _np(replica), **kw)
+
+    def _sum_squares(self):
+        """_norm2 = the squared norm of the whole reduced gradient: the shard's
+        sum of squares in float64, then one exact scalar all_reduce."""
         g = self.own_grad
         if g.is_cuda:
             ops.sumsq(g, self.shard, self._norm2, dtype=_dt(g))
@@ -345,6 +419,14 @@ class ShardedOptimizer:
         if self.world > 1:
             mx.wait(self.dist.all_reduce(self._norm2, self._norm2, 1, op="sum", dtype="f64",
                                          group=self.group))
+
+    def _clip_own_grad(self):
+        """own_grad, final and averaged, scaled by the clip coefficient of the
+        whole reduced gradient: shard sum of squares, one scalar all_reduce,
+        scale. The shards partition the padded gradient, so their sums add up
+        to the full squared norm under reduce="none" as under "rs"."""
+        g = self.own_grad
+        self._sum_squares()
         if g.is_cuda:
             ops.clip_scale(g, self.shard, self._norm2, self.max_grad_norm, dtype=_dt(g))
         else:
@@ -361,7 +443,14 @@ class ShardedOptimizer:
                     p.grad.zero_()
 
     def state_dict(self):
+        if self._fused:
+            return {"step": self.step_count, "master": self.master.clone(),
+                    "exp_avg": self.exp_avg.clone(), "exp_avg_sq": self.exp_avg_sq.clone()}
         return self.opt.state_dict()
 
     def load_state_dict(self, sd):
-        self.opt.load_state_dict(sd)
+        if not self._fused:
+            return self.opt.load_state_dict(sd)
+        self.step_count = int(sd["step"])
+        for name in ("master", "exp_avg", "exp_avg_sq"):
+            getattr(self, name).copy_(sd[name])
